@@ -7,7 +7,12 @@
 A "step" = zero_grad + SPMM.forward (12 encoder passes, 4 losses) + backward + [gradient all-reduce + feature all-gather]
 + clip + AdamW + EMA on one synthetic batch of the pretrain shape (BASELINE.json configs[1]: full 12+6-layer / H=768 model,
 per-GPU batch 128, seq_len 128, queue 36864, train mode with dropout, bf16 compute with fp32 accumulation).  Inputs are
-resident in HBM before the timed region.  Rank 0 prints ONE JSON line."""
+resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what the headline figure does not need: per-launch
+GEMM / cross-attention timing (roofline), clock and power over the timed region, the CPU baseline and, on the default one-GPU workload,
+the other BASELINE configs in child processes.  `--dump-outputs DIR` writes what the last timed step computed (its losses, samples of the
+parameters and queues it left) and an untimed replay of that step from the fixed starting state as DIR/<name>.npy."""
 import argparse
 import json
 import os
@@ -173,6 +178,21 @@ def cpu_baseline(B, Lt, seconds_budget=150.0):
     dt = (time.time() - t0) / n
     return {"value": round(B / dt, 3), "unit": "molecules/s", "cores": cores, "kind": "port",
             "sample": f"oracle/spmm_oracle.py OracleTrainer, full 12+6-layer H=768 model fp32, B={B}, Lt={Lt}, {n} timed step(s) after 1 warm-up"}
+
+
+def seeded_sample(t, n=1 << 20, seed=1234):
+    """A fixed, seeded sample of `n` entries of `t` (flattened), the same positions every run."""
+    t = t.reshape(-1)
+    idx = torch.randint(0, t.numel(), (min(n, t.numel()),), generator=torch.Generator().manual_seed(seed)).sort().values
+    return t[idx.to(t.device)]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, float32."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def child_bench(flags, keep, timeout=420, env=None):
@@ -341,11 +361,15 @@ def main():
     ap.add_argument("--beams", type=int, default=5)
     ap.add_argument("--decode-steps", type=int, default=100)
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short configs[3] (decode) and configs[4]-shape (B=512, Lt=256) "
-                    "measurements the default one-GPU run appends to its JSON line (each in a child process, after the timed region)")
+                    "measurements a --full run of the default one-GPU workload appends to its JSON line (each in a child process, after the timed region)")
     ap.add_argument("--sep-bias", type=float, default=0.0, help="--decode: added to the [SEP] logit of the random-init LM head (0 = [SEP] never wins: every "
                     "molecule decodes all positions)")
     ap.add_argument("--decode-graph", choices=["auto", "on", "off"], default="auto", help="--decode: one hipGraph replay per position instead of eager launches (auto = off since round 5: replay is "
                     "opt-in, it pays only below decode.GRAPH_BELOW_ROWS beam rows per chunk)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: per-launch timing (roofline, "
+                    "cross-attention), clock / power over the timed region, the CPU baseline, the other configs of the default one-GPU run")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write the losses of the last one and seeded samples of the parameters "
+                    "and queues they left as DIR/<name>.npy (float32), plus replay_* files: the same step once more from the fixed starting state")
     args = ap.parse_args()
     # the other configs ride only on the default workload of one GPU (what the driver runs), not on every experiment
     default_run = (args.batch == 128 and args.seq_len == 128 and args.layers == "12,6,6" and args.queue == 36864 and not args.eval_mode and not args.graph
@@ -354,6 +378,8 @@ def main():
         if args.warmup == 10:
             args.warmup = 1
         return decode_bench(args)
+    if not args.full:
+        args.no_kernel_timing = args.no_cpu_baseline = args.no_other_configs = True
     if args.graph:
         args.no_kernel_timing = True
 
@@ -408,23 +434,31 @@ def main():
              'cooldown_epochs': 0}
     tc = {'embed_dim': 256, 'temp': 0.07, 'mlm_probability': 0.15, 'queue_size': args.queue, 'momentum': 0.995, 'alpha': 0.4,
           'schedular': sched, 'optimizer': {'opt': 'adamW', 'lr': 5e-5, 'weight_decay': 0.02}}
-    torch.manual_seed(42)                                   # SPMM_pretrain.py:48 default seed; same init on every rank
     opts = EngineOptions.from_env()
-    model = SPMM(config=tc, spmm_config=cfg, loader_len=1000, options=opts)
-    broadcast_state_([model.store.flat, model.store.flat_m] + [model.store.buffers[k] for k in ("prop_queue", "text_queue")])
-    model.store.refresh_shadows()
-    model.engine.invalidate_banks()
-    model.train(not args.eval_mode)
+
+    def setup():
+        """-> (model, its gradient exchange) in the fixed state every run starts from."""
+        torch.manual_seed(42)                                   # SPMM_pretrain.py:48 default seed; same init on every rank
+        m = SPMM(config=tc, spmm_config=cfg, loader_len=1000, options=opts)
+        broadcast_state_([m.store.flat, m.store.flat_m] + [m.store.buffers[k] for k in ("prop_queue", "text_queue")])
+        m.store.refresh_shadows()
+        m.engine.invalidate_banks()
+        m.train(not args.eval_mode)
+        return m, grad_sync_fn(m.store, opts)
+
+    model, sync = setup()
     B, Lt = args.batch, args.seq_len
     batches = [synthetic_batch(B, Lt, 42 + 1000 * rank + i, dev) for i in range(4)]
-    sync = grad_sync_fn(model.store, opts)
     n_valid = sum(b[3] for b in batches) / len(batches)                # real (non-padding) text tokens per batch
 
-    def one_step(i):
+    def run_step(m, s, i):
         prop, ids, mask, ntok = batches[i % len(batches)]
         if args.graph:                   # the step as one hipGraph replay (dense text layout, single rank): NOT the headline configuration
-            return model.fused_step_graphed(prop, ids, mask, 0.4)
-        return model.fused_step(prop, ids, mask, 0.4, grad_sync=sync, n_tokens=ntok)   # the data pipeline knows the token count (host mask sum)
+            return m.fused_step_graphed(prop, ids, mask, 0.4)
+        return m.fused_step(prop, ids, mask, 0.4, grad_sync=s, n_tokens=ntok)   # the data pipeline knows the token count (host mask sum)
+
+    def one_step(i):
+        return run_step(model, sync, i)
 
     replica_report = {}
 
@@ -487,7 +521,7 @@ def main():
         opt_.step = step_probe
     if hasattr(sync, "wait_events"):
         sync.wait_events = []             # event pair around the compute stream's wait in OverlappedGradSync.finish(), one per timed step
-    smp = smi_sampler(in_process_only=True) if rank == 0 else None       # clock / power of this rank's GPU over the timed region (a 20-Hz in-process reader thread)
+    smp = smi_sampler(in_process_only=True) if rank == 0 and args.full else None       # clock / power of this rank's GPU over the timed region (a 20-Hz in-process reader thread)
     if smp is not None:
         smp.__enter__()
     t0 = time.perf_counter()
@@ -500,6 +534,11 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:        # what the timed steps computed, before anything below runs more steps on the model
+        st = model.store
+        dump_outputs(args.dump_outputs, {"losses": losses, "params_sample": seeded_sample(st.flat), "momentum_params_sample": seeded_sample(st.flat_m),
+                                         "prop_queue_sample": seeded_sample(st.buffers["prop_queue"]),
+                                         "text_queue_sample": seeded_sample(st.buffers["text_queue"])})
     power = None
     if smp is not None:
         smp.__exit__(None, None, None)
@@ -543,6 +582,26 @@ def main():
     mst = torch.cuda.memory_stats(dev)
     hbm = {"peak_allocated_gb": round(mst.get("allocated_bytes.all.peak", 0) / 2**30, 2), "peak_reserved_gb": round(mst.get("reserved_bytes.all.peak", 0) / 2**30, 2),
            "alloc_retries": int(mst.get("num_alloc_retries", 0)), "device_mallocs": int(mst.get("segment.all.allocated", 0))}
+    if args.dump_outputs:
+        # replay_*: the timed path's step once more, untimed, on the batch of the last timed step from the fixed starting state (a fresh
+        # model) -- its losses, gradients and enqueued features are the same to rounding every run, while the state the timed steps leave
+        # drifts a little (fp32 atomics sum gradients in a varying order; AdamW's g / |g| and the similarity-weighted draws of hard negatives
+        # carry that on).  Updated parameters are not replayed: from equal moments AdamW's first update is lr * sign(g).  Every rank runs the
+        # step (it holds the collectives); rank 0 writes.
+        fresh, fresh_sync = setup()
+        ptr = int(fresh.store.buffers["queue_ptr"])
+        fresh_losses = run_step(fresh, fresh_sync, args.warmup + args.steps - 1)
+        torch.cuda.synchronize()
+        if rank == 0:
+            st, cols = fresh.store, slice(ptr, ptr + world * B)
+            dump_outputs(args.dump_outputs, {"replay_losses": fresh_losses, "replay_grads_sample": seeded_sample(st.grad),
+                                             "replay_prop_queue_enqueued": st.buffers["prop_queue"][:, cols],
+                                             "replay_text_queue_enqueued": st.buffers["text_queue"][:, cols]})
+        fresh.engine.tape = None
+        del fresh, fresh_sync, fresh_losses
+        import gc
+        gc.collect()
+        torch.cuda.empty_cache()
 
     # ---- per-kernel timing with HIP events on the launch stream: same step, every GEMM / cross-attention launch bracketed.
     roof, xattn = None, None

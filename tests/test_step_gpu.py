@@ -758,8 +758,8 @@ def test_two_rank_data_parallel_step_on_one_gpu(env):
     envv.pop("GPU_MAX_HW_QUEUES", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8",
-           "--seq-len", "32", "--layers", "2,1,1", "--queue", "64", "--no-cpu-baseline", "--check-replicas"]
-    # no --no-kernel-timing: the instrumented steps after the timed region contain collectives, so every rank must run them
+           "--seq-len", "32", "--layers", "2,1,1", "--queue", "64", "--no-cpu-baseline", "--check-replicas", "--full"]
+    # --full without --no-kernel-timing: the instrumented steps after the timed region contain collectives, so every rank must run them
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=envv, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     assert "replicas identical after" in out.stdout and "queue_ptr = " in out.stdout
