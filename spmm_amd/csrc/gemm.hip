@@ -772,6 +772,8 @@ __global__ __launch_bounds__(512) void gemm_nt_v3_kernel(GemmP p) {
 //  WAR  a slot is restaged >= 2 phases after the phase that read it (A-h0: read P1, restaged P3; W-h1: P2 -> P4; A-h1: P3 ->
 //       next P1), or 1 phase after when an lgkmcnt BEFORE the reading phase's first barrier retired the reads (W-h0: the
 //       four W reads are issued first in P1 and retired by lgkmcnt(8) there; restaged in P2).
+//  The persistent form adds one barrier per wave row at each tile boundary (the rows meet for the epilogue, see there): added
+//  barriers only order more, and since both rows add one, every later barrier still pairs the same phases of the two rows.
 // LDS image of a half-tile: 128 rows x 128 B, 16-B slot index XOR (row>>1)&7 (on the DMA source address and on the read
 // address): every ds_read_b128 lane group of the 16x16x32 operand pattern hits 16 distinct slots.
 constexpr int P8_HT = 128 * BK * 2;        // half-tile: 128 rows x 64 k = 16 KiB
@@ -1197,7 +1199,16 @@ __global__ __launch_bounds__(512) void gemm_nt_p8_kernel(GemmP p) {
     }
     P8_STAMP(2);
 
-    // ---- tile boundary: every wave writes its own 128x64 block (no barrier; the wave rows stay one barrier apart)
+    // ---- tile boundary: every wave writes its own 128x64 block, BOTH wave rows at once.  Inside the K loop the rows run one barrier
+    // apart; left that way, row 0's epilogue would run between two barriers while row 1 multiplies its last quadrant and then waits,
+    // and row 1's between the next two while row 0 multiplies its first quadrant and then waits -- the two epilogues in series, each
+    // SIMD running its epilogue with ONE wave (its LDS round trips, store issue and R / G loads with nothing to hide behind).  One
+    // extra barrier for row 0 here (it waits for row 1's last MFMA cluster) and one for row 1 after the epilogue (row 0 is one
+    // barrier ahead again) put the two waves of a SIMD into the epilogue together.  Barriers are only added, and both rows add one:
+    // every later barrier pairs the same phases as before, so the RAW / WAR argument above is unchanged; the epilogue touches only
+    // the wave's own 4 KiB of P8_XLDS and issues no DMA, so its vmcnt accounting (the `pre` waits) is unchanged as well.
+    if (wr == 0) P8_BAR();
+    P8_SB();
     {
       // everything the epilogue derives from the lane id is computed HERE, per tile: hoisted out of the tile loop it would live
       // across the main loop and spill
@@ -1225,6 +1236,8 @@ __global__ __launch_bounds__(512) void gemm_nt_p8_kernel(GemmP p) {
         else p8_epilogue_blocks<EPI, false, false>(q, acc, xb, mb, nb, lane_e, hook);
       }
     }
+    P8_SB();
+    if (wr == 1) P8_BAR();                           // (pairs with row 0's first barrier of the next tile, or with its final balance)
     P8_STAMP(4);
 #ifdef P8_PROFILE
     ++prof_i;
