@@ -277,6 +277,15 @@ int spmm_lm_loss(const float* logits, const float* logits_m, long ldl, const int
 int spmm_itm_head(const void* xa, long stride_a, const void* xb, long stride_b, int H, const float* W, const float* bias,
                   int n, int B, const float* gscale, float* losses, int loss_slot, float* logits_out, void* dxa, void* dxb,
                   float* dW, float* db, int do_bwd, int x_is_f32, spmm_stream_t stream);
+/* Task head of the fine-tuning models (d_regression.py / d_classification.py / d_classification_multilabel.py): logits[B,C] =
+ * A W2^T + b2 in fp32 from the GELU activations A [B,W] (bf16, row stride lda) and the fp32 masters W2 [C,W], b2 [C]; kind 0 = MSE
+ * (C = 1, target float [B]), 1 = cross entropy (target int32 [B]), 2 = BCE on logits (target float [B,C]).  `loss` (optional) is
+ * WRITTEN with the mean loss.  do_bwd: dA = dlogits W2 (bf16, row stride ldda), dW2 += dlogits^T A, db2 += column sums of dlogits,
+ * dlogits scaled by *gscale (null: 1).  No floating-point atomics: bit-identical results launch to launch.
+ * 1 <= B <= 1024, 1 <= C <= 64, W a multiple of 64 up to 4096. */
+int spmm_task_head(const void* A, long lda, int B, int W, const float* W2, const float* b2, int C, int kind, const void* target,
+                   const float* gscale, float* logits, float* loss, void* dA, long ldda, float* dW2, float* db2, int do_bwd,
+                   spmm_stream_t stream);
 /* property_mtr_head final Linear(H,1) + masked MSE * 5 SPMM_models.py:251-256. */
 int spmm_mpm_head(const void* h, int Lp, int H, const float* w, const float* bias, const float* target, const float* mask,
                   int B, int* n_keep_ws, const float* gscale, float* losses, int loss_slot, float* pred_out, void* dh,

@@ -6,7 +6,7 @@ No HF dependency: the JSON is parsed here and the string "True" of config_bert.j
 from __future__ import annotations
 
 import json
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import List, Tuple
 
 
@@ -140,6 +140,22 @@ def state_spec(cfg: SPMMConfig) -> List[Spec]:
     s += _bert_spec("text_encoder_m.bert.", cfg.text, True) + _mlm_spec("text_encoder_m.", cfg.text)
     s += [("text_proj_m.weight", (E, H), "lin_w"), ("text_proj_m.bias", (E,), "lin_b")]
     return s
+
+
+# head width W (in units of H) and loss of the three fine-tuning models: d_regression.py:24-49, d_classification.py:26-50,
+# d_classification_multilabel.py:26-47 (reg_head = Linear(H, W), GELU, Linear(W, C))
+FINETUNE_TASKS = {"regression": 2, "classification": 1, "multilabel": 1}
+
+
+def finetune_spec(c: BertConfig, task: str, n_output: int = 2) -> List[Spec]:
+    """Every state_dict entry of a reference fine-tuning model, in its order: BertForMaskedLM with layers fusion_layer.. and `cls`
+    replaced by nn.Identity (so text layers 0..f-1 only, no cross-attention), then reg_head.0 [W,H] and reg_head.2 [C,W]."""
+    H = c.hidden_size
+    W = FINETUNE_TASKS[task] * H
+    C = 1 if task == "regression" else int(n_output)
+    s = _bert_spec("text_encoder.bert.", replace(c, num_hidden_layers=c.fusion_layer), False)
+    return s + [("reg_head.0.weight", (W, H), "lin_w"), ("reg_head.0.bias", (W,), "lin_b"),
+                ("reg_head.2.weight", (C, W), "lin_w"), ("reg_head.2.bias", (C,), "lin_b")]
 
 
 MOMENTUM_PAIRS = [("property_encoder.", "property_encoder_m."), ("property_proj.", "property_proj_m."),

@@ -294,6 +294,33 @@ class Engine:
                 self._wg_keep.clear()
                 self._wg_pending = False
 
+    def _pack_plan(self, mask32: torch.Tensor, B: int, Lt: int, n_tokens: Optional[int] = None):
+        """Row bookkeeping for the packed text passes: valid rows of the dense [B*Lt] layout in order, per-sequence start
+        and length.  The packed row count sizes the GEMMs, so the host must know it: either the data pipeline says so
+        (`n_tokens`: the tokenizer's attention mask is a host tensor, its sum costs nothing there -- and the caller then vouches
+        that every mask row is a non-empty prefix, which is what padding='longest' produces) or it is read back from the device,
+        one blocking read per step.  Returns None -- dense fallback -- when a sequence does not start with a valid token
+        (position 0 is what the losses read) or nothing would be saved."""
+        if n_tokens is not None:
+            M = int(n_tokens)
+            if M >= B * Lt:
+                return None
+            # The caller vouches for the hint (SPMM.training_step derives it from the tokenizer's host mask itself).  Best effort
+            # against a wrong one, without a read-back: the mismatch is detected on the device (spmm_pack_plan raises `hint_bad`) and
+            # raises the NaN flag (AdamW, EMA and enqueue become no-ops, as for a non-finite loss, SPMM_models.py:132-134), and the
+            # per-sequence bookkeeping is clamped to the rows the hint sized; launches sized from other derived quantities may still misbehave.
+        else:
+            lens = mask32.sum(1)
+            prefix = (torch.arange(Lt, device=mask32.device)[None, :] < lens[:, None]) == (mask32 != 0)
+            stats = torch.stack([lens.sum(), (lens > 0).sum(), prefix.all().to(lens.dtype)]).cpu()
+            M, nonempty, is_prefix = int(stats[0]), int(stats[1]), int(stats[2])
+            if nonempty != B or not is_prefix or M >= B * Lt:   # holes in the mask: the packed index would not be the position
+                return None
+        if M < 1:
+            return None
+        # valid rows first, original order kept; whatever the hint was, no index leaves the M rows it sized (csrc/plan.hip)
+        return ops.pack_plan(mask32, M, self.hint_bad)
+
     # ---------------------------------------------------------------------------------------- attention launches
     @staticmethod
     def _attn_fwd(Q, K, V, O, lse, *, Lq, Lkv, q_row0=None, q_len=None, kv_row0=None, kv_len=None, **kw):

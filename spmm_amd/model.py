@@ -50,8 +50,8 @@ class _FusedAdamW:
     """AdamW(lr, weight_decay on all params, betas (0.9,0.999), eps 1e-8) SPMM_models.py:340 + clip_grad_norm_(5.) :361
     as three launches over the flat arena; exposes `param_groups[0]['lr']` like a torch optimizer."""
 
-    def __init__(self, store: ParamStore, eng: PretrainStep, lr: float, weight_decay: float):
-        self.store, self.eng = store, eng
+    def __init__(self, store: ParamStore, eng: PretrainStep, lr: float, weight_decay: float, max_norm: float = 5.0):
+        self.store, self.eng, self.max_norm = store, eng, max_norm           # (max_norm = inf: no clipping, the fine-tuning scripts)
         self.param_groups = [{"lr": lr, "weight_decay": weight_decay, "betas": (0.9, 0.999), "eps": 1e-8}]
         dev = store.device
         self.normsq = torch.zeros(1, device=dev)
@@ -72,7 +72,7 @@ class _FusedAdamW:
         ops.grad_sqnorm(self.store.grad, self.normsq)
         ops.adamw_step(self.store.flat, self.store.grad, self.store.adam_m, self.store.adam_v, self.store.shadow, lr=self.eng.lr,
                        beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"], normsq=self.normsq,
-                       max_norm=5.0, step=self.step_count, nan_flag=self.eng.nan_flag, scalars=self.scalars)
+                       max_norm=self.max_norm, step=self.step_count, nan_flag=self.eng.nan_flag, scalars=self.scalars)
         # the transposed weight shadows are operands of the NEXT backward's data-gradient GEMMs only
         self.store.refresh_shadows(transposed_only=True, part="forward")
         self.eng.off_path(lambda: (self.store.refresh_shadows(transposed_only=True, part="transposed"), self.eng.refresh_padded_shadows()))

@@ -372,6 +372,30 @@ def mpm_head(h, Lp, H, w, bias, target, mask, *, B, ws, losses, slot, pred=None,
                _p(pred), _p(dh), _p(dw), _p(db), int(do_bwd), int(h.dtype == torch.float32), _st())
 
 
+TASK_MSE, TASK_CE, TASK_BCE = 0, 1, 2     # spmm_task_head kinds (include/spmm_hip.h)
+
+
+def task_head(A, W2, b2, logits, *, kind, target=None, loss=None, gscale=None, dA=None, dW2=None, db2=None):
+    """Second Linear of the fine-tuning head + its loss (csrc/heads.hip): logits [B,C] fp32 = A W2^T + b2; `loss` (fp32 [1]) is written
+    with the mean loss; with dA / dW2 / db2 the backward runs too (dA written, dW2 / db2 accumulated, scaled by *gscale)."""
+    B, W = A.shape
+    C = W2.shape[0]
+    do_bwd = dA is not None
+    assert A.dtype == BF16 and W2.dtype == torch.float32 and tuple(W2.shape) == (C, W) and tuple(logits.shape) == (B, C)
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and W2.is_contiguous()
+    if target is not None:
+        want = {TASK_MSE: (torch.float32, (B,)), TASK_CE: (torch.int32, (B,)), TASK_BCE: (torch.float32, (B, C))}[kind]
+        assert (target.dtype, tuple(target.shape)) == want and target.is_contiguous(), (target.dtype, target.shape, want)
+    assert b2.dtype == torch.float32 and b2.numel() == C and b2.is_contiguous()
+    if do_bwd:
+        assert dA.dtype == BF16 and tuple(dA.shape) == (B, W) and dA.stride(1) == 1
+        assert dW2.dtype == torch.float32 and tuple(dW2.shape) == (C, W) and dW2.is_contiguous()
+        assert db2.dtype == torch.float32 and db2.numel() == C and db2.is_contiguous()
+    _call("spmm_task_head", _p(A), _row_stride(A), B, W, _p(W2), _p(b2), C, int(kind), _p(target), _p(gscale), _p(logits), _p(loss),
+          _p(dA), 0 if dA is None else _row_stride(dA), _p(dW2), _p(db2), int(do_bwd), _st())
+    return logits
+
+
 def rows_linear(x, W, bias, out, *, act=0):
     """out[r,n] = act(bias[n] + x[r,:] . W[n,:]) in fp32; x [rows, K] fp32 or bf16 (row stride free), W [N, K] fp32 contiguous."""
     rows, K = x.shape

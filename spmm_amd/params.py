@@ -36,9 +36,12 @@ def _layout_order(spec) -> List[str]:
 
 
 class ParamStore:
-    def __init__(self, cfg: SPMMConfig, device, train: bool = True):
+    def __init__(self, cfg: SPMMConfig, device, train: bool = True, spec=None):
+        """`spec`: the entries of another model than SPMM (config.finetune_spec); such a store has no momentum twins and no queues, and
+        its momentum arena and shadow are empty."""
         self.cfg, self.device, self.train = cfg, device, train
-        self.spec = state_spec(cfg)
+        twins = spec is None
+        self.spec = state_spec(cfg) if twins else list(spec)
         self.shape = {n: s for n, s, _ in self.spec}
         self.kind = {n: k for n, _, k in self.spec}
         self.order = _layout_order(self.spec)
@@ -51,9 +54,9 @@ class ParamStore:
         self.total = off
         f32 = dict(dtype=torch.float32, device=device)
         self.flat = torch.zeros(self.total, **f32)
-        self.flat_m = torch.zeros(self.total, **f32)
+        self.flat_m = torch.zeros(self.total if twins else 0, **f32)
         self.shadow = torch.zeros(self.total, dtype=torch.bfloat16, device=device)
-        self.shadow_m = torch.zeros(self.total, dtype=torch.bfloat16, device=device)
+        self.shadow_m = torch.zeros(self.total if twins else 0, dtype=torch.bfloat16, device=device)
         if train:
             self.grad = torch.zeros(self.total, **f32)
             self.adam_m = torch.zeros(self.total, **f32)
@@ -151,7 +154,8 @@ class ParamStore:
         "transposed" = only the data-gradient GEMMs' transposed shadows (read by the next BACKWARD: Engine.off_path), "all" = both."""
         if not transposed_only:
             ops.cast_f32_bf16(self.flat, self.shadow)
-            ops.cast_f32_bf16(self.flat_m, self.shadow_m)
+            if self.flat_m.numel():
+                ops.cast_f32_bf16(self.flat_m, self.shadow_m)
         if part in ("all", "forward"):
             self.refresh_frag(False)
             if not transposed_only:
