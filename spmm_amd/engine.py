@@ -21,6 +21,7 @@ device memory; the one host read per step is the packed row count that sizes the
 from __future__ import annotations
 
 import contextlib
+import functools
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -122,6 +123,28 @@ class Group:
         self.kv_idx = idx.to(torch.int32)
         return self
 
+    def cross_layout(self) -> dict:
+        """Layout arguments of this group's cross-attention launches (forward, backward, fused form)."""
+        src = self.src
+        return dict(kmask=self.kv_mask, kv_seq=self.kv_idx, q_row0=self.q_row0, q_len=self.q_len,
+                    kv_row0=None if src is None else src.row0, kv_len=None if src is None else src.len)
+
+
+@dataclass
+class Batch:
+    """A token-major batch as the layers see it: its groups and -- when only the device knows it -- its row count.  The fusion batch of
+    the packed path ends with the text hard negatives drawn on the device: their total length, and so the batch's row count, is device
+    data; the batch is allocated for the most it can be and every launch over ITS rows takes the real count from `rows_dev` ("device-side
+    row counts" in include/spmm_hip.h).  Launches over other row sets (key/value sources, SelfKV) never do."""
+    groups: List[Group]
+    rows_dev: Optional[torch.Tensor] = None      # int32 [1] on the device; None: the host-side row count is exact
+
+    def __iter__(self):
+        return iter(self.groups)
+
+    def __len__(self):
+        return len(self.groups)
+
 
 STREAM_TOKENS_MAX = 49152         # B x Lt above which the step runs on one stream (Engine._one_stream)
 
@@ -176,10 +199,9 @@ class Engine:
         self.force_one_stream = False     # set by the data-parallel schedule check (model.py::_schedule_check)
         self._wg_stream, self._wg_pending, self._wg_keep = None, False, []
         self._salt = 0
-        self._off_path_ok, self._pre_bwd = False, None     # (set per step by SPMM.fused_step: single-rank runs only)
-        self._dyn = None                  # (rows a batch is allocated for, int32 [1] device tensor with the rows it really has): step.py, fusion batch
+        self._off_path_ok, self._pre_bwd = False, None     # (set per step by SPMM.fused_step: single-rank runs, data-parallel ones with dp_four_streams)
+        self._xattn_checked = self._xattn_off = False       # fused cross-attention: one-time self-check done / failed (_attn_block_fwd)
         self.tape = None
-        self.last32 = None
         E, Q = cfg.embed_dim, cfg.queue_size
         self._bank = None          # queue GEMM shadows, sized on first use (depend on the local batch)
 
@@ -204,13 +226,6 @@ class Engine:
     def _on(side):
         return torch.cuda.stream(side) if side is not None else contextlib.nullcontext()
 
-    def _md(self, t):
-        """Device-side row count for launches over the batch `t` belongs to (None: its host-side row count is exact).  The fusion batch of
-        the packed path ends with the text hard negatives drawn on the device: their total length -- and so the batch's row count -- is
-        device data; the batch is allocated for the most it can be and every launch over it takes the real count from device memory."""
-        d = self._dyn
-        return d[1] if (d is not None and t.shape[0] == d[0]) else None
-
     def _new(self, *shape, dtype=BF):
         return torch.empty(*shape, dtype=dtype, device=self.dev)
 
@@ -231,14 +246,13 @@ class Engine:
         return self.P.wT(key, src_fp32)
 
     def _wgrad(self, dY, X, gW, gb=None, inline=False, md=None):
-        """gW[N,K] += dY[M,N]^T X[M,K] ; gb[N] += column sums of dY (TN GEMM: no transposed copies).
+        """gW[N,K] += dY[M,N]^T X[M,K] ; gb[N] += column sums of dY (TN GEMM: no transposed copies).  md: device-side row count of dY / X.
         Nothing on the backward's critical path reads a weight gradient, so (unless `inline`) the two launches go to a side stream
         behind an event on the current one: they fill the CUs the data-gradient chain leaves idle (attention / LayerNorm backward,
         tails of small-M GEMMs).  All weight gradients share ONE such stream (accumulations into the same tensor stay ordered);
         `wgrad_join()` makes the current stream wait for it (before a layer's gradient exchange, before the optimiser)."""
         ws = None if inline else self._wgrad_side()
         C = gW.view(dY.shape[1], X.shape[1])
-        md = self._md(dY) if md is None else md
         if ws is None:
             if gb is not None:
                 ops.colsum_bf16(dY, gb, R_dev=md)
@@ -294,6 +308,11 @@ class Engine:
                 self._wg_keep.clear()
                 self._wg_pending = False
 
+    def end_backward(self):
+        """The weight gradients of the side stream are complete from here on; their operands and the tape are released."""
+        self.wgrad_join(release=True)
+        self.tape = None
+
     def _pack_plan(self, mask32: torch.Tensor, B: int, Lt: int, n_tokens: Optional[int] = None):
         """Row bookkeeping for the packed text passes: valid rows of the dense [B*Lt] layout in order, per-sequence start
         and length.  The packed row count sizes the GEMMs, so the host must know it: either the data pipeline says so
@@ -321,184 +340,186 @@ class Engine:
         # valid rows first, original order kept; whatever the hint was, no index leaves the M rows it sized (csrc/plan.hip)
         return ops.pack_plan(mask32, M, self.hint_bad)
 
-    # ---------------------------------------------------------------------------------------- attention launches
-    @staticmethod
-    def _attn_fwd(Q, K, V, O, lse, *, Lq, Lkv, q_row0=None, q_len=None, kv_row0=None, kv_len=None, **kw):
-        """Kernels keep <= 256 rows of K / V on chip; longer (dense) sequences go through the chunked path of ops.py."""
-        if Lq <= ops.ATTN_MAXL and Lkv <= ops.ATTN_MAXL:
-            return ops.attn_fwd(Q, K, V, O, lse, Lq=Lq, Lkv=Lkv, q_row0=q_row0, q_len=q_len, kv_row0=kv_row0, kv_len=kv_len, **kw)
-        if q_row0 is not None or kv_row0 is not None:
-            raise ValueError("packed layouts are limited to %d-token sequences" % ops.ATTN_MAXL)
-        return ops.attn_fwd_long(Q, K, V, O, lse, Lq=Lq, Lkv=Lkv, **kw)
-
-    @staticmethod
-    def _attn_bwd(Q, K, V, O, lse, dO, dQ, dK, dV, *, Lq, Lkv, q_row0=None, q_len=None, kv_row0=None, kv_len=None, **kw):
-        if Lq <= ops.ATTN_MAXL and Lkv <= ops.ATTN_MAXL:
-            return ops.attn_bwd(Q, K, V, O, lse, dO, dQ, dK, dV, Lq=Lq, Lkv=Lkv, q_row0=q_row0, q_len=q_len, kv_row0=kv_row0,
-                                kv_len=kv_len, **kw)
-        if q_row0 is not None or kv_row0 is not None:
-            raise ValueError("packed layouts are limited to %d-token sequences" % ops.ATTN_MAXL)
-        return ops.attn_bwd_long(Q, K, V, O, lse, dO, dQ, dK, dV, Lq=Lq, Lkv=Lkv, **kw)
-
     # ---------------------------------------------------------------------------------------- attention block
-    def _ln_res(self, x, X, X32, gamma, beta, y, **kw):
+    def _ln_res(self, x, X, X32, gamma, beta, y, md, **kw):
         """y = LN(dropout(x) + residual): the residual is X (bf16) or, with the fp32 residual stream (EngineOptions.resid_fp32), X32;
         returns the fp32 twin of y in that mode (None otherwise)."""
         if X32 is None:
-            ops.ln_fwd(x, X, gamma, beta, y, rows_dev=self._md(x), **kw)
+            ops.ln_fwd(x, X, gamma, beta, y, rows_dev=md, **kw)
             return None
+        assert md is None                                        # (spmm_ln_fwd_r32 takes no device-side row count)
         y32 = self._new(*y.shape, dtype=torch.float32)
         ops.ln_fwd_r32(x, X32, gamma, beta, y, y32=y32, **kw)
         return y32
 
-    def _proj_ln(self, A, Wb, bias, resid, X32, gamma, beta, *, save, eps, ph):
+    def _proj_ln(self, A, Wb, bias, resid, X32, gamma, beta, *, save, eps, ph, salt, md=None):
         """y = LayerNorm(dropout(A W^T + b) + resid): BertSelfOutput / BertOutput (xbert.py:369-373, 447-451): the projection GEMM, then
         dropout + residual + LayerNorm in one row kernel (the pre-norm sum z is formed in fp32 registers; its bf16 copy is kept for the
-        backward, which regenerates the dropout mask from (seed, salt)).  -> (y, z, mean, rstd, salt, y32)"""
+        backward, which regenerates the dropout mask from (seed, salt)).  md: device-side row count of A.  -> (y, z, mean, rstd, y32)"""
         M, H = A.shape[0], Wb.shape[0]
         x, y = self._new(M, H), self._new(M, H)
         mean = self._new(M, dtype=torch.float32) if save else None
         rstd = self._new(M, dtype=torch.float32) if save else None
-        salt = self._next_salt()
-        ops.gemm_nt(A, Wb, x, bias=bias, M_dev=self._md(A))
+        ops.gemm_nt(A, Wb, x, bias=bias, M_dev=md)
         # The backward recovers the normalised values from the OUTPUT y (spmm_ln_bwd, beta_from_y): the pre-norm sum is not stored -- one
         # write pass per residual LayerNorm less, and the projection's output buffer is free again at once (EngineOptions.ln_from_y;
         # the fp32 residual stream keeps the stored sum)
         from_y = self.opt.ln_from_y and X32 is None
-        y32 = self._ln_res(x, resid, X32, gamma, beta, y, zout=x if (save and not from_y) else None, mean=mean, rstd=rstd, eps=eps, dropout_p=ph,
-                           seed=self.seed, salt=salt)
-        return y, (None if from_y else x), mean, rstd, salt, y32
+        y32 = self._ln_res(x, resid, X32, gamma, beta, y, md, zout=x if (save and not from_y) else None, mean=mean, rstd=rstd, eps=eps,
+                           dropout_p=ph, seed=self.seed, salt=salt)
+        return y, (None if from_y else x), mean, rstd, y32
 
     def _attn_block_fwd(self, pfx, c, X, groups, save, cross, X32=None):
-        """BertAttention.forward xbert.py:401-422 on a token batch.  cross=True uses g.kv as key/value source.
+        """BertAttention.forward xbert.py:401-422 on a token batch.  cross=True uses the groups' key/value sources.
         -> (y, tape entry, fp32 twin of y or None)."""
-        P, H, nH, M = self.P, c.hidden_size, c.num_attention_heads, X.shape[0]
-        pa, ph = self._p_attn(c), self._p_hidden(c)
-        sv = {"X": X, "lse": [], "salt_a": [], "cross": cross}
-        ctx = self._new(M, H)
+        P, H, nH = self.P, c.hidden_size, c.num_attention_heads
+        # Every form of the block draws its salts here, in one order (every group's attention salt, then the hidden one): the composite of
+        # launches, the fused one-launch form and the composite that replaces a fused form that failed its self-check draw the same masks
+        salts_a = [self._next_salt() for _ in groups]
+        salt_h = self._next_salt()
+        sv = {"X": X, "salt_a": salts_a, "salt_h": salt_h, "cross": cross}
         if not cross:
-            Wqkv = P.fused(pfx + ".self.", ("query", "key", "value"), "weight")
-            bqkv = P.fused(pfx + ".self.", ("query", "key", "value"), "bias", what="w")
-            QKV = self._new(M, 3 * H)
-            ops.gemm_nt(X, Wqkv, QKV, bias=bqkv, M_dev=self._md(X))
-            sv["QKV"] = QKV
-            skv = sv["SKV"] = {}                                 # K/V of the groups' private self-attention sources (SelfKV), one GEMM each
-            for g in groups:
-                lse = self._new(g.nseq, nH, g.L, dtype=torch.float32) if save else None
-                salt = self._next_salt()
-                r = g.rows
-                if g.self_src is not None:
-                    # query rows = a subset of their sequences' rows (here: position 0 only); keys / values = every token of the
-                    # sequence, projected from the layer input with the key / value rows of the fused weight
-                    if id(g.self_src) not in skv:
-                        skv[id(g.self_src)] = ops.gemm_nt(g.self_src.x, Wqkv[H:], self._new(g.self_src.x.shape[0], 2 * H), bias=bqkv[H:],
-                                                          M_dev=g.self_src.rows_dev)
-                    KVs = skv[id(g.self_src)]
-                    self._attn_fwd(QKV[r, :H], KVs[:, :H], KVs[:, H:], ctx[r], lse, nseq=g.nseq, nH=nH, Lq=g.L, Lkv=g.skv_L,
-                                   kmask=None, causal_from=g.nseq, dropout_p=pa, seed=self.seed, salt=salt,
-                                   q_row0=g.q_row0, q_len=g.q_len, kv_row0=g.skv_row0, kv_len=g.skv_len)
-                else:
-                    self._attn_fwd(QKV[r, :H], QKV[r, H:2 * H], QKV[r, 2 * H:], ctx[r], lse, nseq=g.nseq, nH=nH, Lq=g.L, Lkv=g.L,
-                                   kmask=g.kmask, causal_from=g.causal_from, dropout_p=pa, seed=self.seed, salt=salt,
-                                   q_row0=g.q_row0, q_len=g.q_len, kv_row0=g.q_row0, kv_len=g.q_len)
-                sv["lse"].append(lse)
-                sv["salt_a"].append(salt)
+            ctx, core = self._self_attn_fwd(pfx, c, X, groups, save, salts_a)
         else:
-            Qc = self._new(M, H)
-            ops.gemm_nt(X, P.wb(pfx + ".self.query.weight"), Qc, bias=P.w(pfx + ".self.query.bias"), M_dev=self._md(X))
-            Wkv = P.fused(pfx + ".self.", ("key", "value"), "weight")
-            bkv = P.fused(pfx + ".self.", ("key", "value"), "bias", what="w")
-            sv["Qc"], sv["KV"] = Qc, []
-            shared = {}                                          # K/V of a shared source: projected once per layer
+            sv["Qc"] = Qc = ops.gemm_nt(X, P.wb(pfx + ".self.query.weight"), self._new(X.shape[0], H), bias=P.w(pfx + ".self.query.bias"),
+                                        M_dev=groups.rows_dev)
+            kv_of = functools.partial(self._xattn_kv, P.fused(pfx + ".self.", ("key", "value"), "weight"),
+                                      P.fused(pfx + ".self.", ("key", "value"), "bias", what="w"), {})
             fx = self.opt.fused_xattn
-            fused = (fx is True or fx == "all" or (fx == "nograd" and not save)) and not getattr(self, "_xattn_off", False) and X32 is None and self._md(X) is None and all(ops.xattn_supported(H, nH, g.L, g.Lkv) for g in groups)
+            fused = ((fx is True or fx == "all" or (fx == "nograd" and not save)) and not self._xattn_off and X32 is None
+                     and groups.rows_dev is None and all(ops.xattn_supported(H, nH, g.L, g.Lkv) for g in groups))
             if fused:
-                # ONE launch per group for core + output projection + dropout + residual + LayerNorm (csrc/xattn.hip); the salts are
-                # drawn in the composite's order (every group's attention salt, then the hidden one): both forms draw the same masks
-                salts_a = [self._next_salt() for _ in groups]
-                salt_h = self._next_salt()
-                y = self._new(M, H)
-                z = self._new(M, H) if save else None
-                mean = self._new(M, dtype=torch.float32) if save else None
-                rstd = self._new(M, dtype=torch.float32) if save else None
-                if not save:
-                    ctx = None
-                WoF = P.wF(pfx + ".output.dense.weight")
-            for gi, g in enumerate(groups):
-                if g.src is not None:
-                    if id(g.src) not in shared:
-                        shared[id(g.src)] = ops.gemm_nt(g.src.kv, Wkv, self._new(g.src.kv.shape[0], 2 * H), bias=bkv)
-                    KV = shared[id(g.src)]
-                else:
-                    KV = self._new(g.nseq * g.Lkv, 2 * H)
-                    ops.gemm_nt(g.kv, Wkv, KV, bias=bkv)
-                lse = self._new(g.nseq, nH, g.L, dtype=torch.float32) if save else None
-                r = g.rows
-                src = g.src
-                lay = dict(kmask=g.kv_mask, kv_seq=g.kv_idx, q_row0=g.q_row0, q_len=g.q_len,
-                           kv_row0=None if src is None else src.row0, kv_len=None if src is None else src.len)
+                y, out = self._xattn_fused_fwd(pfx, c, X, Qc, kv_of, groups, save, salts_a, salt_h)
+                g0 = groups.groups[0]
+                if not self._xattn_checked and not ops._DRY_RUN and g0.row0 == 0:
+                    self._xattn_checked = True
+                    agrees, dmax, dmean = self._xattn_agrees(pfx, c, X, Qc, out["KV"][0], g0, y, salts_a[0], salt_h)
+                    if not agrees:
+                        # Not fatal: the composite of launches is always available.  This process stops using the one-launch form and says
+                        # so (a default path must not be able to end a run; the kernel's own parity tests compare it directly).  The
+                        # composite below runs with the salts drawn above: from here on the masks are those of fused_xattn="off".
+                        import warnings
+                        warnings.warn(f"spmm_amd: the fused cross-attention kernel disagrees with the composite launches (max |dy| {dmax:.3g}, "
+                                      f"mean {dmean:.3g}); falling back to the composite for this process (SPMM_FUSED_XATTN=off)")
+                        streams.note("fused cross-attention kernel failed its one-time self-check: composite launches used instead")
+                        self._xattn_off = True
+                        fused = False
                 if fused:
-                    salt = salts_a[gi]
-                    ops.xattn_fwd(Qc[r], KV[:, :H], KV[:, H:], WoF, P.w(pfx + ".output.dense.bias"), X[r], P.w(pfx + ".output.LayerNorm.weight"),
-                                  P.w(pfx + ".output.LayerNorm.bias"), y[r], nseq=g.nseq, nH=nH, Lq=g.L, Lkv=g.Lkv, eps=c.layer_norm_eps,
-                                  Z=None if z is None else z[r], mean=None if mean is None else mean[r.start:r.stop],
-                                  rstd=None if rstd is None else rstd[r.start:r.stop], CTX=None if ctx is None else ctx[r], lse=lse,
-                                  attn_dropout_p=pa, salt_a=salt, hidden_dropout_p=ph, salt_h=salt_h, seed=self.seed, row_base=r.start, **lay)
-                    if r.start == 0 and not getattr(self, "_xattn_checked", False) and not ops._DRY_RUN:
-                        # one-time self-check of the fused kernel against the composite launches on the first block it serves (same
-                        # dropout masks: same seed, salts and row counter).  The kernel keeps asynchronously loaded registers in
-                        # flight behind hand-counted waits: a compiler change that broke that would corrupt y silently.
-                        self._xattn_checked = True
-                        n = r.stop
-                        c2, x2, y2 = self._new(n, H), self._new(n, H), self._new(n, H)
-                        self._attn_fwd(Qc[r], KV[:, :H], KV[:, H:], c2, None, nseq=g.nseq, nH=nH, Lq=g.L, Lkv=g.Lkv, is_cross=True,
-                                       dropout_p=pa, seed=self.seed, salt=salt, **lay)
-                        ops.gemm_nt(c2, P.wb(pfx + ".output.dense.weight"), x2, bias=P.w(pfx + ".output.dense.bias"))
-                        ops.ln_fwd(x2, X[r], P.w(pfx + ".output.LayerNorm.weight"), P.w(pfx + ".output.LayerNorm.bias"), y2,
-                                   eps=c.layer_norm_eps, dropout_p=ph, seed=self.seed, salt=salt_h)
-                        d = (y[r].float() - y2.float()).abs()
-                        scale = max(1.0, float(y2.float().abs().max()) / 8.0)              # (outlier channels of a trained model scale the roundings)
-                        if not (float(d.max()) < 0.25 * scale and float(d.mean()) < 5e-3 * scale):      # (bf16 roundings of x differ: ~1e-3 on average)
-                            # Not fatal: the composite of launches is always available.  This process stops using the one-launch form and
-                            # says so (a default path must not be able to end a run; the kernel's own parity tests compare it directly).
-                            import warnings
-                            warnings.warn(f"spmm_amd: the fused cross-attention kernel disagrees with the composite launches (max |dy| {float(d.max()):.3g}, "
-                                          f"mean {float(d.mean()):.3g}); falling back to the composite for this process (SPMM_FUSED_XATTN=off)")
-                            streams.note("fused cross-attention kernel failed its one-time self-check: composite launches used instead")
-                            self._xattn_off = True
-                            return self._attn_block_fwd(pfx, c, X, groups, save, cross, X32=X32)
-                else:
-                    salt = self._next_salt()
-                    self._attn_fwd(Qc[r], KV[:, :H], KV[:, H:], ctx[r], lse, nseq=g.nseq, nH=nH, Lq=g.L, Lkv=g.Lkv, is_cross=True,
-                                   dropout_p=pa, seed=self.seed, salt=salt, **lay)
-                sv["KV"].append(KV)
-                sv["lse"].append(lse)
-                sv["salt_a"].append(salt)
-            if fused:
-                sv.update(ctx=ctx, z=z, y=y, mean=mean, rstd=rstd, salt_h=salt_h)
-                return y, (sv if save else None), None
-        y, x, mean, rstd, salt, y32 = self._proj_ln(ctx, P.wb(pfx + ".output.dense.weight"), P.w(pfx + ".output.dense.bias"), X, X32,
-                                                    P.w(pfx + ".output.LayerNorm.weight"), P.w(pfx + ".output.LayerNorm.bias"), save=save,
-                                                    eps=c.layer_norm_eps, ph=ph)
-        sv.update(ctx=ctx, z=x, y=y, mean=mean, rstd=rstd, salt_h=salt)
+                    sv.update(out)
+                    return y, (sv if save else None), None
+            ctx, core = self._xattn_core_fwd(c, Qc, kv_of, groups, save, salts_a)
+        y, z, mean, rstd, y32 = self._proj_ln(ctx, P.wb(pfx + ".output.dense.weight"), P.w(pfx + ".output.dense.bias"), X, X32,
+                                              P.w(pfx + ".output.LayerNorm.weight"), P.w(pfx + ".output.LayerNorm.bias"), save=save,
+                                              eps=c.layer_norm_eps, ph=self._p_hidden(c), salt=salt_h, md=groups.rows_dev)
+        sv.update(core, ctx=ctx, z=z, y=y, mean=mean, rstd=rstd)
         return y, (sv if save else None), y32
+
+    def _self_attn_fwd(self, pfx, c, X, groups, save, salts):
+        """Self-attention core: the fused Q/K/V projection of the batch, then one attention launch per group.  -> (ctx, tape fields)"""
+        P, H, nH, M = self.P, c.hidden_size, c.num_attention_heads, X.shape[0]
+        Wqkv = P.fused(pfx + ".self.", ("query", "key", "value"), "weight")
+        bqkv = P.fused(pfx + ".self.", ("query", "key", "value"), "bias", what="w")
+        QKV = ops.gemm_nt(X, Wqkv, self._new(M, 3 * H), bias=bqkv, M_dev=groups.rows_dev)
+        ctx, lses = self._new(M, H), []
+        skv = {}                                                 # K/V of the groups' private self-attention sources (SelfKV), one GEMM each
+        for g, salt in zip(groups, salts):
+            lse = self._new(g.nseq, nH, g.L, dtype=torch.float32) if save else None
+            r = g.rows
+            kw = dict(nseq=g.nseq, nH=nH, Lq=g.L, dropout_p=self._p_attn(c), seed=self.seed, salt=salt, q_row0=g.q_row0, q_len=g.q_len)
+            if g.self_src is not None:
+                # query rows = a subset of their sequences' rows (here: position 0 only); keys / values = every token of the
+                # sequence, projected from the layer input with the key / value rows of the fused weight
+                if id(g.self_src) not in skv:
+                    skv[id(g.self_src)] = ops.gemm_nt(g.self_src.x, Wqkv[H:], self._new(g.self_src.x.shape[0], 2 * H), bias=bqkv[H:],
+                                                      M_dev=g.self_src.rows_dev)
+                KVs = skv[id(g.self_src)]
+                ops.attn_fwd_long(QKV[r, :H], KVs[:, :H], KVs[:, H:], ctx[r], lse, Lkv=g.skv_L, kmask=None, causal_from=g.nseq,
+                                  kv_row0=g.skv_row0, kv_len=g.skv_len, **kw)
+            else:
+                ops.attn_fwd_long(QKV[r, :H], QKV[r, H:2 * H], QKV[r, 2 * H:], ctx[r], lse, Lkv=g.L, kmask=g.kmask, causal_from=g.causal_from,
+                                  kv_row0=g.q_row0, kv_len=g.q_len, **kw)
+            lses.append(lse)
+        return ctx, dict(QKV=QKV, SKV=skv, lse=lses)
+
+    def _xattn_kv(self, Wkv, bkv, done, g):
+        """Projected keys | values [source rows, 2H] of group g's cross-attention source; a shared source (KVSource) is projected once per
+        layer (`done`: what this block has projected so far)."""
+        key, kv = (id(g), g.kv) if g.src is None else (id(g.src), g.src.kv)
+        if key not in done:
+            done[key] = ops.gemm_nt(kv, Wkv, self._new(kv.shape[0], Wkv.shape[0]), bias=bkv)
+        return done[key]
+
+    def _xattn_core_fwd(self, c, Qc, kv_of, groups, save, salts):
+        """Composite cross-attention core: per group the key/value projection of its source (if new), then the attention launch.
+        -> (ctx, tape fields)"""
+        H, nH = c.hidden_size, c.num_attention_heads
+        ctx, KVs, lses = self._new(Qc.shape[0], H), [], []
+        for g, salt in zip(groups, salts):
+            KV = kv_of(g)
+            lse = self._new(g.nseq, nH, g.L, dtype=torch.float32) if save else None
+            ops.attn_fwd_long(Qc[g.rows], KV[:, :H], KV[:, H:], ctx[g.rows], lse, nseq=g.nseq, nH=nH, Lq=g.L, Lkv=g.Lkv, is_cross=True,
+                              dropout_p=self._p_attn(c), seed=self.seed, salt=salt, **g.cross_layout())
+            KVs.append(KV)
+            lses.append(lse)
+        return ctx, dict(KV=KVs, lse=lses)
+
+    def _xattn_fused_fwd(self, pfx, c, X, Qc, kv_of, groups, save, salts, salt_h):
+        """The cross-attention block as ONE launch per group for core + output projection + dropout + residual + LayerNorm
+        (csrc/xattn.hip), behind the same projections as the composite.  -> (y, tape fields)"""
+        P, H, nH, M = self.P, c.hidden_size, c.num_attention_heads, X.shape[0]
+        y = self._new(M, H)
+        z, ctx = (self._new(M, H), self._new(M, H)) if save else (None, None)
+        mean = self._new(M, dtype=torch.float32) if save else None
+        rstd = self._new(M, dtype=torch.float32) if save else None
+        WoF = P.wF(pfx + ".output.dense.weight")
+        KVs, lses = [], []
+        for g, salt in zip(groups, salts):
+            KV = kv_of(g)
+            lse = self._new(g.nseq, nH, g.L, dtype=torch.float32) if save else None
+            r = g.rows
+            ops.xattn_fwd(Qc[r], KV[:, :H], KV[:, H:], WoF, P.w(pfx + ".output.dense.bias"), X[r], P.w(pfx + ".output.LayerNorm.weight"),
+                          P.w(pfx + ".output.LayerNorm.bias"), y[r], nseq=g.nseq, nH=nH, Lq=g.L, Lkv=g.Lkv, eps=c.layer_norm_eps,
+                          Z=None if z is None else z[r], mean=None if mean is None else mean[r.start:r.stop],
+                          rstd=None if rstd is None else rstd[r.start:r.stop], CTX=None if ctx is None else ctx[r], lse=lse,
+                          attn_dropout_p=self._p_attn(c), salt_a=salt, hidden_dropout_p=self._p_hidden(c), salt_h=salt_h, seed=self.seed,
+                          row_base=r.start, **g.cross_layout())
+            KVs.append(KV)
+            lses.append(lse)
+        return y, dict(KV=KVs, lse=lses, ctx=ctx, z=z, y=y, mean=mean, rstd=rstd)
+
+    def _xattn_agrees(self, pfx, c, X, Qc, KV, g, y, salt_a, salt_h):
+        """One-time self-check of the fused kernel: its output `y` on the rows of group g (the batch's first rows) against the composite
+        launches with the same dropout masks (same seed, salts and row counter).  The kernel keeps asynchronously loaded registers in
+        flight behind hand-counted waits: a compiler change that broke that would corrupt y silently.  A host read.
+        -> (agrees, max |dy|, mean |dy|)"""
+        P, H, r = self.P, c.hidden_size, g.rows
+        c2, x2, y2 = self._new(r.stop, H), self._new(r.stop, H), self._new(r.stop, H)
+        ops.attn_fwd_long(Qc[r], KV[:, :H], KV[:, H:], c2, None, nseq=g.nseq, nH=c.num_attention_heads, Lq=g.L, Lkv=g.Lkv, is_cross=True,
+                          dropout_p=self._p_attn(c), seed=self.seed, salt=salt_a, **g.cross_layout())
+        ops.gemm_nt(c2, P.wb(pfx + ".output.dense.weight"), x2, bias=P.w(pfx + ".output.dense.bias"))
+        ops.ln_fwd(x2, X[r], P.w(pfx + ".output.LayerNorm.weight"), P.w(pfx + ".output.LayerNorm.bias"), y2,
+                   eps=c.layer_norm_eps, dropout_p=self._p_hidden(c), seed=self.seed, salt=salt_h)
+        d = (y[r].float() - y2.float()).abs()
+        dmax, dmean = float(d.max()), float(d.mean())
+        scale = max(1.0, float(y2.float().abs().max()) / 8.0)              # (outlier channels of a trained model scale the roundings)
+        return dmax < 0.25 * scale and dmean < 5e-3 * scale, dmax, dmean    # (bf16 roundings of x differ: ~1e-3 on average)
 
     def _attn_block_bwd(self, pfx, c, sv, dY, groups, dkv_acc):
         """-> dX (bf16).  Parameter gradients accumulate into the flat grad arena; cross-attention key/value source
         gradients accumulate (fp32) into dkv_acc[i] for group i."""
         P, H, nH = self.P, c.hidden_size, c.num_attention_heads
-        X, M = sv["X"], sv["X"].shape[0]
+        X, M, md = sv["X"], sv["X"].shape[0], groups.rows_dev
         pa, ph = self._p_attn(c), self._p_hidden(c)
         dz = self._new(M, H)
         dx = self._new(M, H) if ph > 0 else dz
         from_y = sv["z"] is None                          # (the forward kept no pre-norm sum: normalised values from the output, _proj_ln)
         ops.ln_bwd(dY, sv["y"] if from_y else sv["z"], sv["mean"], sv["rstd"], P.w(pfx + ".output.LayerNorm.weight"), dz, dx=dx if ph > 0 else None,
                    dgamma=P.g(pfx + ".output.LayerNorm.weight"), dbeta=P.g(pfx + ".output.LayerNorm.bias"), dropout_p=ph,
-                   seed=self.seed, salt=sv["salt_h"], dxsum=P.g(pfx + ".output.dense.bias"), rows_dev=self._md(dY),
+                   seed=self.seed, salt=sv["salt_h"], dxsum=P.g(pfx + ".output.dense.bias"), rows_dev=md,
                    beta_from_y=P.w(pfx + ".output.LayerNorm.bias") if from_y else None)
-        self._wgrad(dx, sv["ctx"], P.g(pfx + ".output.dense.weight"))
+        self._wgrad(dx, sv["ctx"], P.g(pfx + ".output.dense.weight"), md=md)
         dctx = self._new(M, H)
-        ops.gemm_nt(dx, self._wT(pfx + ".output.dense", P.w(pfx + ".output.dense.weight")), dctx, M_dev=self._md(dx))
+        ops.gemm_nt(dx, self._wT(pfx + ".output.dense", P.w(pfx + ".output.dense.weight")), dctx, M_dev=md)
         dX = self._new(M, H)
         if not sv["cross"]:
             QKV = sv["QKV"]
@@ -508,25 +529,24 @@ class Engine:
             dskv = {}
             for i, g in enumerate(groups):
                 r = g.rows
+                kw = dict(nseq=g.nseq, nH=nH, Lq=g.L, dropout_p=pa, seed=self.seed, salt=sv["salt_a"][i], q_row0=g.q_row0, q_len=g.q_len)
                 if g.self_src is not None:
                     if id(g.self_src) not in dskv:               # rows no sequence owns (zero rows past a negative's length) stay zero
                         dskv[id(g.self_src)] = (g.self_src, self._zeros(g.self_src.x.shape[0], 2 * H))
                     KVs, dKVs = sv["SKV"][id(g.self_src)], dskv[id(g.self_src)][1]
-                    self._attn_bwd(QKV[r, :H], KVs[:, :H], KVs[:, H:], sv["ctx"][r], sv["lse"][i], dctx[r], dQKV[r, :H], dKVs[:, :H], dKVs[:, H:],
-                                   nseq=g.nseq, nH=nH, Lq=g.L, Lkv=g.skv_L, kmask=None, causal_from=g.nseq, dropout_p=pa, seed=self.seed,
-                                   salt=sv["salt_a"][i], q_row0=g.q_row0, q_len=g.q_len, kv_row0=g.skv_row0, kv_len=g.skv_len)
+                    ops.attn_bwd_long(QKV[r, :H], KVs[:, :H], KVs[:, H:], sv["ctx"][r], sv["lse"][i], dctx[r], dQKV[r, :H], dKVs[:, :H], dKVs[:, H:],
+                                      Lkv=g.skv_L, kmask=None, causal_from=g.nseq, kv_row0=g.skv_row0, kv_len=g.skv_len, **kw)
                     ops.zero_(dQKV[r, H:])                       # the batch rows' own keys / values were never attended
                     continue
-                self._attn_bwd(QKV[r, :H], QKV[r, H:2 * H], QKV[r, 2 * H:], sv["ctx"][r], sv["lse"][i], dctx[r], dQKV[r, :H],
-                             dQKV[r, H:2 * H], dQKV[r, 2 * H:], nseq=g.nseq, nH=nH, Lq=g.L, Lkv=g.L, kmask=g.kmask,
-                             causal_from=g.causal_from, dropout_p=pa, seed=self.seed, salt=sv["salt_a"][i],
-                             q_row0=g.q_row0, q_len=g.q_len, kv_row0=g.q_row0, kv_len=g.q_len)
-            self._wgrad(dQKV, X, gWqkv, gbqkv)
+                ops.attn_bwd_long(QKV[r, :H], QKV[r, H:2 * H], QKV[r, 2 * H:], sv["ctx"][r], sv["lse"][i], dctx[r], dQKV[r, :H],
+                                  dQKV[r, H:2 * H], dQKV[r, 2 * H:], Lkv=g.L, kmask=g.kmask, causal_from=g.causal_from,
+                                  kv_row0=g.q_row0, kv_len=g.q_len, **kw)
+            self._wgrad(dQKV, X, gWqkv, gbqkv, md=md)
             WT = self._wT(pfx + ".self.qkv", P.fused(pfx + ".self.", ("query", "key", "value"), "weight", what="w"))
             for src, dKVs in dskv.values():                      # key / value projections of the private sources: weight and data gradient
                 self._wgrad(dKVs, src.x, gWqkv[H:], gbqkv[H:], md=src.rows_dev)
                 ops.gemm_nt(dKVs, WT[:, H:], src.dx, M_dev=src.rows_dev)
-            ops.gemm_nt(dQKV, WT, dX, R=dz, M_dev=self._md(dQKV))
+            ops.gemm_nt(dQKV, WT, dX, R=dz, M_dev=md)
         else:
             Qc = sv["Qc"]
             dQc = self._new(M, H)
@@ -544,10 +564,9 @@ class Engine:
                     dKV = pool[id(src)][1][g.kv_off * g.Lkv:(g.kv_off + g.nseq) * g.Lkv]
                 else:
                     dKV = self._new(g.nseq * g.Lkv, 2 * H)
-                self._attn_bwd(Qc[r], KV[:, :H], KV[:, H:], sv["ctx"][r], sv["lse"][i], dctx[r], dQc[r], dKV[:, :H], dKV[:, H:],
-                             nseq=g.nseq, nH=nH, Lq=g.L, Lkv=g.Lkv, kmask=g.kv_mask, is_cross=True, dropout_p=pa, seed=self.seed,
-                             salt=sv["salt_a"][i], kv_seq=g.kv_idx, q_row0=g.q_row0, q_len=g.q_len,
-                             kv_row0=None if src is None else src.row0, kv_len=None if src is None else src.len)
+                ops.attn_bwd_long(Qc[r], KV[:, :H], KV[:, H:], sv["ctx"][r], sv["lse"][i], dctx[r], dQc[r], dKV[:, :H], dKV[:, H:],
+                                  nseq=g.nseq, nH=nH, Lq=g.L, Lkv=g.Lkv, is_cross=True, dropout_p=pa, seed=self.seed, salt=sv["salt_a"][i],
+                                  **g.cross_layout())
                 if src is None:
                     self._wgrad(dKV, g.kv, gWkv, gbkv)
                     ops.gemm_nt(dKV, WkvT, dkv_acc[i], epi=ops.EPI_F32_ACC)
@@ -558,8 +577,8 @@ class Engine:
                     dKVu = ops.gather_rows(self._new(src.pack_idx.numel(), 2 * H), dKVu, src.pack_idx)
                 self._wgrad(dKVu, src.kv, gWkv, gbkv)
                 ops.gemm_nt(dKVu, WkvT, dkv_acc[id(src)], epi=ops.EPI_F32_ACC)
-            self._wgrad(dQc, X, P.g(pfx + ".self.query.weight"), P.g(pfx + ".self.query.bias"))
-            ops.gemm_nt(dQc, self._wT(pfx + ".self.query", P.w(pfx + ".self.query.weight")), dX, R=dz, M_dev=self._md(dQc))
+            self._wgrad(dQc, X, P.g(pfx + ".self.query.weight"), P.g(pfx + ".self.query.bias"), md=md)
+            ops.gemm_nt(dQc, self._wT(pfx + ".self.query", P.w(pfx + ".self.query.weight")), dX, R=dz, M_dev=md)
         return dX
 
     # ------------------------------------------------------------------------------------------------- layers
@@ -575,44 +594,43 @@ class Engine:
         # backward epilogue is a plain multiply -- the erf / exp work of xbert.py:436's backward leaves the dgrad GEMM
         dact = self._new(M, I) if save else None
         ops.gemm_nt(a, P.wb(lp + "intermediate.dense.weight"), h, bias=P.w(lp + "intermediate.dense.bias"),
-                    epi=ops.EPI_GELU_DERIV if save else ops.EPI_GELU, C2=dact, M_dev=self._md(a))
-        y, x, mean, rstd, salt, y32 = self._proj_ln(h, P.wb(lp + "output.dense.weight"), P.w(lp + "output.dense.bias"), a, a32,
-                                                    P.w(lp + "output.LayerNorm.weight"), P.w(lp + "output.LayerNorm.bias"), save=save,
-                                                    eps=c.layer_norm_eps, ph=self._p_hidden(c))
+                    epi=ops.EPI_GELU_DERIV if save else ops.EPI_GELU, C2=dact, M_dev=groups.rows_dev)
+        salt = self._next_salt()
+        y, x, mean, rstd, y32 = self._proj_ln(h, P.wb(lp + "output.dense.weight"), P.w(lp + "output.dense.bias"), a, a32,
+                                              P.w(lp + "output.LayerNorm.weight"), P.w(lp + "output.LayerNorm.bias"), save=save,
+                                              eps=c.layer_norm_eps, ph=self._p_hidden(c), salt=salt, md=groups.rows_dev)
         sv = dict(att=sv1, cross=sv2, a=a, h=h, dact=dact, z=x, y=y, mean=mean, rstd=rstd, salt=salt) if save else None
         return y, sv, y32
 
     def _layer_bwd(self, lp, c, sv, dY, groups, dkv_acc):
-        P, H, I, M = self.P, c.hidden_size, c.intermediate_size, dY.shape[0]
+        P, H, I, M, md = self.P, c.hidden_size, c.intermediate_size, dY.shape[0], groups.rows_dev
         ph = self._p_hidden(c)
         dz = self._new(M, H)
         dx = self._new(M, H) if ph > 0 else dz
         from_y = sv["z"] is None
         ops.ln_bwd(dY, sv["y"] if from_y else sv["z"], sv["mean"], sv["rstd"], P.w(lp + "output.LayerNorm.weight"), dz, dx=dx if ph > 0 else None,
                    dgamma=P.g(lp + "output.LayerNorm.weight"), dbeta=P.g(lp + "output.LayerNorm.bias"), dropout_p=ph,
-                   seed=self.seed, salt=sv["salt"], dxsum=P.g(lp + "output.dense.bias"), rows_dev=self._md(dY),
+                   seed=self.seed, salt=sv["salt"], dxsum=P.g(lp + "output.dense.bias"), rows_dev=md,
                    beta_from_y=P.w(lp + "output.LayerNorm.bias") if from_y else None)
-        self._wgrad(dx, sv["h"], P.g(lp + "output.dense.weight"))
+        self._wgrad(dx, sv["h"], P.g(lp + "output.dense.weight"), md=md)
         dpre = self._new(M, I)
         ops.gemm_nt(dx, self._wT(lp + "output.dense", P.w(lp + "output.dense.weight")), dpre,
-                    epi=ops.EPI_MUL, G=sv["dact"], colsum=P.g(lp + "intermediate.dense.bias"),
-                    M_dev=self._md(dx))
-        self._wgrad(dpre, sv["a"], P.g(lp + "intermediate.dense.weight"))
+                    epi=ops.EPI_MUL, G=sv["dact"], colsum=P.g(lp + "intermediate.dense.bias"), M_dev=md)
+        self._wgrad(dpre, sv["a"], P.g(lp + "intermediate.dense.weight"), md=md)
         da = self._new(M, H)
-        ops.gemm_nt(dpre, self._wT(lp + "intermediate.dense", P.w(lp + "intermediate.dense.weight")), da, R=dz, M_dev=self._md(dpre))
+        ops.gemm_nt(dpre, self._wT(lp + "intermediate.dense", P.w(lp + "intermediate.dense.weight")), da, R=dz, M_dev=md)
         if sv["cross"] is not None:
             da = self._attn_block_bwd(lp + "crossattention", c, sv["cross"], da, groups, dkv_acc)
         return self._attn_block_bwd(lp + "attention", c, sv["att"], da, groups, None)
 
     def stack_fwd(self, pfx, c, layers, has_cross, X, groups, save, X32=None):
-        """-> (y, tape).  With X32 (the fp32 twin of X: EngineOptions.resid_fp32) the residual stream runs in fp32 and the fp32 twin of
-        y is left in `self.last32`."""
+        """groups: the Batch X holds.  -> (y, tape, y32).  With X32 (the fp32 twin of X: EngineOptions.resid_fp32) the residual stream runs
+        in fp32 and y32 is the fp32 twin of y (None otherwise)."""
         tape = []
         for i in layers:
             X, sv, X32 = self._layer_fwd(f"{pfx}encoder.layer.{i}.", c, has_cross and i >= c.fusion_layer, X, groups, save, X32=X32)
             tape.append(sv)
-        self.last32 = X32
-        return X, tape
+        return X, tape, X32
 
     def stack_bwd(self, pfx, c, layers, tape, dY, groups, dkv_acc=None):
         for i, sv in zip(reversed(list(layers)), reversed(tape)):
@@ -707,14 +725,8 @@ class Engine:
         # wgrad of the tied decoder: dWord[V,H] += dlogits^T y ; dbias += colsum
         # (inline: the tied word-embedding gradient is also written by embed_bwd's atomics on the compute stream)
         self._wgrad(dlogits[:, :V], sv["y"], P.g(pfx + "bert.embeddings.word_embeddings.weight"), P.g(pfx + "cls.predictions.bias"), inline=True)
-        key = pfx + "cls.decoderT"
-        if key not in self.P._wT:           # [H, Vpad] zero-padded transposed shadow (K of the dgrad GEMM must be %64)
-            self.P._wT[key] = torch.zeros(H, Vp, dtype=BF, device=self.dev)
-            self.P._wT_pad = getattr(self.P, "_wT_pad", {})
-            self.P._wT_pad[key] = (pfx + "bert.embeddings.word_embeddings.weight", V)
-            self.refresh_padded_shadows()
         dy = self._new(M, H)
-        ops.gemm_nt(dlogits, self.P._wT[key], dy)
+        ops.gemm_nt(dlogits, P.wT_padded(pfx + "cls.decoderT", pfx + "bert.embeddings.word_embeddings.weight", Vp), dy)
         dz = self._new(M, H)
         ops.ln_bwd(dy, sv["z"], sv["mean"], sv["rstd"], P.w(pfx + "cls.predictions.transform.LayerNorm.weight"), dz,
                    dgamma=P.g(pfx + "cls.predictions.transform.LayerNorm.weight"), dbeta=P.g(pfx + "cls.predictions.transform.LayerNorm.bias"))
@@ -724,10 +736,6 @@ class Engine:
         dX = self._new(M, H) if out is None else out
         ops.gemm_nt(dpre, self._wT(pfx + "cls.transform", P.w(pfx + "cls.predictions.transform.dense.weight")), dX)
         return dX
-
-    def refresh_padded_shadows(self):
-        for key, (name, V) in getattr(self.P, "_wT_pad", {}).items():
-            self.P._wT[key][:, :V].copy_(self.P.w(name).t())
 
     def _gelu_bwd(self, dz, pre):
         """elementwise dz * gelu'(pre) (small head tensors only)."""

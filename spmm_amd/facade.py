@@ -20,7 +20,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .engine import BF, Group
+from .engine import BF, Batch, Group
 
 
 def _i32(mask, nseq, L, dev):
@@ -65,10 +65,10 @@ class BertFacade:
             kvm = _i32(encoder_attention_mask, nseq, Lkv, dev)
         lo, hi = {"text": (0, c.fusion_layer), "fusion": (c.fusion_layer, c.num_hidden_layers),
                   "multi_modal": (0, c.num_hidden_layers)}[mode]
-        g = [Group(0, nseq, L, _i32(attention_mask, nseq, L, dev), 0 if is_decoder else nseq, kv=kv, Lkv=Lkv, kv_mask=kvm)]
+        g = Batch([Group(0, nseq, L, _i32(attention_mask, nseq, L, dev), 0 if is_decoder else nseq, kv=kv, Lkv=Lkv, kv_mask=kvm)])
         if self.has_cross and hi > c.fusion_layer and kv is None:
             raise AssertionError("encoder_hidden_states must be given for cross-attention layers")     # xbert.py:495
-        y, _ = eng.stack_fwd(self.pfx, c, range(lo, hi), self.has_cross, x, g, False)
+        y, _, _ = eng.stack_fwd(self.pfx, c, range(lo, hi), self.has_cross, x, g, False)
         out = y.view(nseq, L, H).float()
         return SimpleNamespace(last_hidden_state=out) if return_dict else (out,)
 

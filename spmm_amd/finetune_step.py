@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .engine import Engine, Group
+from .engine import Batch, Engine, Group
 
 PFX = "text_encoder.bert."
 TASK_KIND = {"regression": ops.TASK_MSE, "classification": ops.TASK_CE, "multilabel": ops.TASK_BCE}
@@ -48,12 +48,12 @@ class FinetuneStep(Engine):
         if pk:
             M = pk["M"]
             x = ops.gather_rows2(self._new(M, H), x, pk["rows"])
-            groups = [Group(0, B, L, None, B, q_row0=pk["row0"], q_len=pk["len"], nrows=M)]
+            groups = Batch([Group(0, B, L, None, B, q_row0=pk["row0"], q_len=pk["len"], nrows=M)])
             cls_idx = pk["row0_64"]
         else:
-            groups = [Group(0, B, L, mask32, B)]
+            groups = Batch([Group(0, B, L, mask32, B)])
             cls_idx = torch.arange(B, dtype=torch.int64, device=self.dev) * L
-        y, tape = self.stack_fwd(PFX, c, range(0, f), False, x, groups, save)
+        y, tape, _ = self.stack_fwd(PFX, c, range(0, f), False, x, groups, save)
         cls = ops.gather_rows2(self._new(B, H), y, cls_idx)
         W2 = P.w("reg_head.2.weight")
         Wd, C = W2.shape[1], W2.shape[0]
@@ -103,6 +103,4 @@ class FinetuneStep(Engine):
         ep = PFX + "embeddings."
         ops.embed_bwd(0, dz, nseq=B, L=L, H=H, dpos=P.g(ep + "position_embeddings.weight"), dtype0=P.g(ep + "token_type_embeddings.weight"),
                       ids=T["ids32"], dword=P.g(ep + "word_embeddings.weight"))
-        self.wgrad_join(release=True)
-        self._wg_pending = False
-        self.tape = None
+        self.end_backward()

@@ -75,7 +75,7 @@ class _FusedAdamW:
                        max_norm=self.max_norm, step=self.step_count, nan_flag=self.eng.nan_flag, scalars=self.scalars)
         # the transposed weight shadows are operands of the NEXT backward's data-gradient GEMMs only
         self.store.refresh_shadows(transposed_only=True, part="forward")
-        self.eng.off_path(lambda: (self.store.refresh_shadows(transposed_only=True, part="transposed"), self.eng.refresh_padded_shadows()))
+        self.eng.off_path(lambda: (self.store.refresh_shadows(transposed_only=True, part="transposed"), self.store.refresh_padded_shadows()))
 
     @property
     def grad_norm(self) -> torch.Tensor:
@@ -203,7 +203,7 @@ class SPMM(_Base):
         # below (current stream) must land AFTER it
         self.engine.pre_backward_wait()
         missing, unexpected = self.store.load_state_dict(state_dict, strict=strict)
-        self.engine.refresh_padded_shadows()
+        self.store.refresh_padded_shadows()
         self.engine.invalidate_banks()
         return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
 
@@ -341,7 +341,8 @@ class SPMM(_Base):
         check = self._schedule_check_begin(grad_sync)
         eng.alpha.fill_(float(alpha))
         eng.gscale.fill_(1.0)
-        # (single rank only: beside RCCL's stream the weight-gradient stream shares a hardware slot with the caller's stream -- queue index
+        # (single-rank runs, and data-parallel ones with EngineOptions.dp_four_streams and a non-exclusive exchange; otherwise,
+        #  beside RCCL's stream, the weight-gradient stream shares a hardware slot with the caller's stream -- queue index
         #  4 = 0 mod 4 -- and two streams that wait for each other there run the step at 74-76 ms instead of 57, profiles/r06_dp_one_rank.txt)
         eng._off_path_ok = grad_sync is None or (self.options.dp_four_streams and getattr(grad_sync, "exclusive", True) is False)
         eng.off_path(lambda: ops.zero_(self.store.grad))        # nothing reads or writes a gradient before the backward

@@ -517,10 +517,13 @@ def _chunks(L, step=128):
 
 
 def attn_fwd_long(Q, K, V, O, lse, *, nseq, nH, Lq, Lkv, kmask=None, causal_from=None, is_cross=False, dropout_p=0.0, seed=None,
-                  salt=0, kv_seq=None):
+                  salt=0, kv_seq=None, q_row0=None, q_len=None, kv_row0=None, kv_len=None):
+    """attn_fwd for sequences of any length: the one dispatch point between the single launch and the chunked path."""
     if Lq <= ATTN_MAXL and Lkv <= ATTN_MAXL:
         return attn_fwd(Q, K, V, O, lse, nseq=nseq, nH=nH, Lq=Lq, Lkv=Lkv, kmask=kmask, causal_from=causal_from, is_cross=is_cross,
-                        dropout_p=dropout_p, seed=seed, salt=salt, kv_seq=kv_seq)
+                        dropout_p=dropout_p, seed=seed, salt=salt, kv_seq=kv_seq, q_row0=q_row0, q_len=q_len, kv_row0=kv_row0, kv_len=kv_len)
+    if q_row0 is not None or kv_row0 is not None:
+        raise ValueError("packed layouts are limited to %d-token sequences" % ATTN_MAXL)
     dev, H = Q.device, nH * 64
     nsrc = K.shape[0] // Lkv
     ar_q = torch.arange(nseq, dtype=torch.int32, device=dev)
@@ -548,11 +551,14 @@ def attn_fwd_long(Q, K, V, O, lse, *, nseq, nH, Lq, Lkv, kmask=None, causal_from
 
 
 def attn_bwd_long(Q, K, V, O, lse, dO, dQ, dK, dV, *, nseq, nH, Lq, Lkv, kmask=None, causal_from=None, is_cross=False, dropout_p=0.0,
-                  seed=None, salt=0, kv_seq=None):
+                  seed=None, salt=0, kv_seq=None, q_row0=None, q_len=None, kv_row0=None, kv_len=None):
     """dK / dV: [nseq*Lkv, H] views when kv_seq is given (per query sequence), else [sources*Lkv, H]."""
     if Lq <= ATTN_MAXL and Lkv <= ATTN_MAXL:
         return attn_bwd(Q, K, V, O, lse, dO, dQ, dK, dV, nseq=nseq, nH=nH, Lq=Lq, Lkv=Lkv, kmask=kmask, causal_from=causal_from,
-                        is_cross=is_cross, dropout_p=dropout_p, seed=seed, salt=salt, kv_seq=kv_seq)
+                        is_cross=is_cross, dropout_p=dropout_p, seed=seed, salt=salt, kv_seq=kv_seq, q_row0=q_row0, q_len=q_len,
+                        kv_row0=kv_row0, kv_len=kv_len)
+    if q_row0 is not None or kv_row0 is not None:
+        raise ValueError("packed layouts are limited to %d-token sequences" % ATTN_MAXL)
     dev, H = Q.device, nH * 64
     nsrc = K.shape[0] // Lkv
     nkv_out = nseq if kv_seq is not None else nsrc

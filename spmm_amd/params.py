@@ -71,6 +71,7 @@ class ParamStore:
             elif k == "ptr":
                 self.buffers[n] = torch.zeros(1, dtype=torch.long, device=device)
         self._wT: Dict[str, torch.Tensor] = {}     # transposed bf16 shadows for dgrad, keyed by (fused) name
+        self._wT_pad: Dict[str, str] = {}          # ... those of them that are zero-padded copies (wT_padded): key -> parameter name
         self._wF: Dict[str, tuple] = {}            # fused cross-attention: name -> (bf16 shadow view, fragment-ordered image, is momentum)
 
     # ---- views -----------------------------------------------------------------------------------------------
@@ -130,6 +131,20 @@ class ParamStore:
             self._wT_src[key] = src
             ops.cast_transpose(src, None, self._wT[key])
         return self._wT[key]
+
+    def wT_padded(self, key: str, name: str, cols: int) -> torch.Tensor:
+        """Transposed bf16 shadow [in, cols] of the student weight `name` [out, in], zero-padded from `out` to `cols` columns (K of a
+        data-gradient GEMM must be a multiple of 64); refreshed by refresh_padded_shadows()."""
+        if key not in self._wT:
+            self._wT[key] = torch.zeros(self.w(name).shape[1], cols, dtype=torch.bfloat16, device=self.device)
+            self._wT_pad[key] = name
+            self.refresh_padded_shadows()
+        return self._wT[key]
+
+    def refresh_padded_shadows(self):
+        for key, name in self._wT_pad.items():
+            w = self.w(name)
+            self._wT[key][:, :w.shape[0]].copy_(w.t())
 
     def wF(self, name: str) -> torch.Tensor:
         """Fragment-ordered bf16 image of a cross-attention output-projection weight (csrc/xattn.hip: every wave-level load of the

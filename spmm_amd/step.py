@@ -6,7 +6,7 @@ from typing import Callable, Optional, Tuple
 import torch
 
 from . import ops
-from .engine import STREAM_TOKENS_MAX, BF, LOSS_ITA, LOSS_ITM, LOSS_MLM, LOSS_MPM, Engine, Group, KVSource, SelfKV, _ceil
+from .engine import STREAM_TOKENS_MAX, BF, LOSS_ITA, LOSS_ITM, LOSS_MLM, LOSS_MPM, Batch, Engine, Group, KVSource, SelfKV, _ceil
 
 
 class PretrainStep(Engine):
@@ -20,7 +20,7 @@ class PretrainStep(Engine):
         Batch layout (csrc/plan.hip): [PV queries pe | pe[neg] | pe] [text packed te | te] [LM pass] [causal PV] [text negatives, PACKED].
         Which sequences were drawn as text negatives is device data, so the LENGTH of that last part -- and with it the batch's row count --
         is known only on the device: the batch is allocated for B x Lt such rows and every launch over it reads the real row count from
-        device memory (`Engine._dyn`, "device-side row counts" in include/spmm_hip.h): no padding row is computed, no host read sizes
+        device memory (`Batch.rows_dev` in engine.py, "device-side row counts" in include/spmm_hip.h): no padding row is computed, no host read sizes
         anything.  Every index array comes from ONE launch (spmm_fusion_plan); the batch and the top layer's input are two row gathers."""
         cfg = self.cfg
         ct = cfg.text
@@ -35,25 +35,22 @@ class PretrainStep(Engine):
         src_pv = KVSource(prop_embeds.view(B * Lp, H), B, Lp).preset(4 * B, fp["start_p"], fp["list_p"])
         src_text = KVSource(text_embeds, B, Lt, row0=pk["row0"], length=pk["len"], pack_idx=pk["rows"]).preset(4 * B, fp["start_t"], fp["list_t"])
         ar = fp["ar"]
-        g_lo = [Group(0, 3 * B, Lp, None, 3 * B).bind(src_text, fp["kvidx_pv"], 0),
-                Group(o_tp, 2 * B, Lt, None, 2 * B, q_row0=fp["qrow0_tp"], q_len=fp["qlen_tp"], nrows=2 * M).bind(src_pv, fp["kvidx_tp"], 0),
-                Group(o_lm, B, Lt, mask32, 0).bind(src_pv, ar, 2 * B),
-                Group(o_12, B, Lp, None, 0).bind(src_text, ar, 3 * B),
-                Group(o_8, B, Lt, None, B, q_row0=fp["row0_8"], q_len=fp["len_8"], nrows=B * Lt).bind(src_pv, ar, 3 * B)]
-        self._dyn = (Rcap, fp["rows_dev"])
-        try:
-            y, tape_lo = self.stack_fwd("text_encoder.bert.", ct, range(f, n - 1), True, X6, g_lo, save)
-        finally:
-            self._dyn = None
+        g_lo = Batch([Group(0, 3 * B, Lp, None, 3 * B).bind(src_text, fp["kvidx_pv"], 0),
+                      Group(o_tp, 2 * B, Lt, None, 2 * B, q_row0=fp["qrow0_tp"], q_len=fp["qlen_tp"], nrows=2 * M).bind(src_pv, fp["kvidx_tp"], 0),
+                      Group(o_lm, B, Lt, mask32, 0).bind(src_pv, ar, 2 * B),
+                      Group(o_12, B, Lp, None, 0).bind(src_text, ar, 3 * B),
+                      Group(o_8, B, Lt, None, B, q_row0=fp["row0_8"], q_len=fp["len_8"], nrows=B * Lt).bind(src_pv, ar, 3 * B)],
+                     rows_dev=fp["rows_dev"])
+        y, tape_lo, _ = self.stack_fwd("text_encoder.bert.", ct, range(f, n - 1), True, X6, g_lo, save)
         ntop = 6 * B + B * Lt + B * Lp
         Xtop = ops.gather_rows2(self._new(ntop, H), y, fp["idx_top"])
         skv_a = SelfKV(y[:o_lm])                                # rows of the PV and packed-text ITM sequences
         skv_b = SelfKV(y[o_8:], rows_dev=fp["mn_dev"])          # rows of the packed text negatives (device-side count)
-        g_top = [Group(0, 3 * B, 1, None, 3 * B, self_src=skv_a, skv_row0=fp["skv_row0_pv"], skv_len=fp["skv_len_pv"], skv_L=Lp).bind(src_text, fp["kvidx_pv"], 0),
-                 Group(3 * B, 2 * B, 1, None, 2 * B, self_src=skv_a, skv_row0=fp["skv_row0_tx"], skv_len=fp["skv_len_tx"], skv_L=Lt).bind(src_pv, fp["kvidx_tp"], 0),
-                 Group(5 * B, B, 1, None, B, self_src=skv_b, skv_row0=fp["row0_8"], skv_len=fp["len_8"], skv_L=Lt).bind(src_pv, ar, 3 * B),
-                 Group(6 * B, B, Lt, mask32, 0).bind(src_pv, ar, 2 * B),
-                 Group(6 * B + B * Lt, B, Lp, None, 0).bind(src_text, ar, 3 * B)]
+        g_top = Batch([Group(0, 3 * B, 1, None, 3 * B, self_src=skv_a, skv_row0=fp["skv_row0_pv"], skv_len=fp["skv_len_pv"], skv_L=Lp).bind(src_text, fp["kvidx_pv"], 0),
+                       Group(3 * B, 2 * B, 1, None, 2 * B, self_src=skv_a, skv_row0=fp["skv_row0_tx"], skv_len=fp["skv_len_tx"], skv_L=Lt).bind(src_pv, fp["kvidx_tp"], 0),
+                       Group(5 * B, B, 1, None, B, self_src=skv_b, skv_row0=fp["row0_8"], skv_len=fp["len_8"], skv_L=Lt).bind(src_pv, ar, 3 * B),
+                       Group(6 * B, B, Lt, mask32, 0).bind(src_pv, ar, 2 * B),
+                       Group(6 * B + B * Lt, B, Lp, None, 0).bind(src_text, ar, 3 * B)])
         ytop, sv_top, _ = self._layer_fwd(f"text_encoder.bert.encoder.layer.{n - 1}.", ct, True, Xtop, g_top, save)
         return dict(fp=fp, ytop=ytop, sv_top=sv_top, g_top=g_top, skv=(skv_a, skv_b), g_lo=g_lo, tape_lo=tape_lo, src_text=src_text, src_pv=src_pv,
                     o_tp=o_tp, o_lm=o_lm, o_12=o_12, o_8=o_8, ntop=ntop, Rcap=Rcap)
@@ -74,11 +71,7 @@ class PretrainStep(Engine):
             self._layer_done(f"text_encoder.bert.encoder.layer.{n - 1}.")
         ops.add_rows_bf16(dX6, fp["idx_top"][:6 * B], dXtop[:6 * B])     # ... plus, at position 0, what came through the queries
         dX6[o_lm:o_8].copy_(dXtop[6 * B:])
-        self._dyn = (S6["Rcap"], fp["rows_dev"])
-        try:
-            return self.stack_bwd("text_encoder.bert.", ct, range(f, n - 1), S6["tape_lo"], dX6, S6["g_lo"], dkv_acc=dkv_acc)
-        finally:
-            self._dyn = None
+        return self.stack_bwd("text_encoder.bert.", ct, range(f, n - 1), S6["tape_lo"], dX6, S6["g_lo"], dkv_acc=dkv_acc)
 
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, prop: torch.Tensor, ids: torch.Tensor, mask: torch.Tensor, *, mpm_mask: Optional[torch.Tensor] = None,
@@ -130,12 +123,12 @@ class PretrainStep(Engine):
                 x2 = ops.gather_rows2(self._new(M + B * Lt, H), x2d, pk["gidx2"])
                 if r32:
                     x2_32 = torch.cat([x2_32[:B * Lt].index_select(0, pk["rows"]), x2_32[B * Lt:]])
-                g2 = [Group(0, B, Lt, None, B, q_row0=pk["row0"], q_len=pk["len"], nrows=M), Group(M, B, Lt, mask32, 0)]
+                g2 = Batch([Group(0, B, Lt, None, B, q_row0=pk["row0"], q_len=pk["len"], nrows=M), Group(M, B, Lt, mask32, 0)])
             else:
-                g2 = [Group(0, 2 * B, Lt, torch.cat([mask32, mask32]), B)]
-            y2, tape2 = self.stack_fwd("text_encoder.bert.", ct, range(0, f), True, x2, g2, save, X32=x2_32)
+                g2 = Batch([Group(0, 2 * B, Lt, torch.cat([mask32, mask32]), B)])
+            y2, tape2, y2_32 = self.stack_fwd("text_encoder.bert.", ct, range(0, f), True, x2, g2, save, X32=x2_32)
             text_embeds, hidden10 = y2[:M], y2[M:]
-            text_embeds_32, hidden10_32 = (self.last32[:M], self.last32[M:]) if r32 else (None, None)
+            text_embeds_32, hidden10_32 = (y2_32[:M], y2_32[M:]) if r32 else (None, None)
         side_m = self._fork(1)
         ema_done = None
         with self._on(side_m):
@@ -156,7 +149,7 @@ class PretrainStep(Engine):
                 x4 = ops.gather_rows2(self._new(2 * M, H), x4d, pk["gidx4"])
                 if r32:
                     x4_32 = torch.cat([x4_32[:B * Lt].index_select(0, pk["rows"]), x4_32[B * Lt:].index_select(0, pk["rows"])])
-                g4 = [g2[0], Group(M, B, Lt, None, 0, q_row0=pk["row0"], q_len=pk["len"], nrows=M)]
+                g4 = Batch([g2.groups[0], Group(M, B, Lt, None, 0, q_row0=pk["row0"], q_len=pk["len"], nrows=M)])
             else:
                 g4 = g2
             cls_m = bool(pk) and self.opt.cls_only_top and not r32 and f >= 1
@@ -164,38 +157,37 @@ class PretrainStep(Engine):
                 # text_embeds_m feeds only position 0 to a loss (text_feat_m, :105): the momentum text encoder's LAST unimodal layer runs on
                 # [position 0 of the B packed sequences | every row of the causal copy], the position-0 queries attending keys / values
                 # projected from the full sequences (engine.SelfKV; the student's counterpart is a key / value source of the fusion layers)
-                y4, _ = self.stack_fwd("text_encoder_m.bert.", ct, range(0, f - 1), True, x4, g4, False)
+                y4, _, _ = self.stack_fwd("text_encoder_m.bert.", ct, range(0, f - 1), True, x4, g4, False)
                 x4t = ops.gather_rows2(self._new(B + M, H), y4, pk["idx_m"])
-                g4t = [Group(0, B, 1, None, B, self_src=SelfKV(y4[:M]), skv_row0=pk["row0"], skv_len=pk["len"], skv_L=Lt),
-                       Group(B, B, Lt, None, 0, q_row0=pk["row0"], q_len=pk["len"], nrows=M)]
+                g4t = Batch([Group(0, B, 1, None, B, self_src=SelfKV(y4[:M]), skv_row0=pk["row0"], skv_len=pk["len"], skv_L=Lt),
+                             Group(B, B, Lt, None, 0, q_row0=pk["row0"], q_len=pk["len"], nrows=M)])
                 y4t, _, _ = self._layer_fwd(f"text_encoder_m.bert.encoder.layer.{f - 1}.", ct, False, x4t, g4t, False)
                 text_embeds_m, hidden9 = y4t[:B], y4t[B:]          # (position-0 rows only)
             else:
-                y4, _ = self.stack_fwd("text_encoder_m.bert.", ct, range(0, f), True, x4, g4, False, X32=x4_32)
+                y4, _, y4_32 = self.stack_fwd("text_encoder_m.bert.", ct, range(0, f), True, x4, g4, False, X32=x4_32)
                 text_embeds_m, hidden9 = y4[:M], y4[M:]
-            text_embeds_m_32, hidden9_32 = (self.last32[:M], self.last32[M:]) if r32 else (None, None)
+            text_embeds_m_32, hidden9_32 = (y4_32[:M], y4_32[M:]) if r32 else (None, None)
         x1, esv1 = self.embed_pv("property_encoder.", cp, prop, mpm_mask, 2 * B, B, save)
-        g1 = [Group(0, 2 * B, Lp, None, B)]
-        y1, tape1 = self.stack_fwd("property_encoder.", cp, range(cp.num_hidden_layers), False, x1, g1, save, X32=f32(x1))
+        g1 = Batch([Group(0, 2 * B, Lp, None, B)])
+        y1, tape1, y1_32 = self.stack_fwd("property_encoder.", cp, range(cp.num_hidden_layers), False, x1, g1, save, X32=f32(x1))
         prop_embeds, prop_embeds_causal = y1[:B * Lp], y1[B * Lp:]
-        prop_embeds_32, prop_embeds_causal_32 = (self.last32[:B * Lp], self.last32[B * Lp:]) if r32 else (None, None)
+        prop_embeds_32, prop_embeds_causal_32 = (y1_32[:B * Lp], y1_32[B * Lp:]) if r32 else (None, None)
         if ema_done is not None:
             torch.cuda.current_stream().wait_event(ema_done)
         x3, _ = self.embed_pv("property_encoder_m.", cp, prop, mpm_mask, B, B, False)
-        prop_embeds_m, _ = self.stack_fwd("property_encoder_m.", cp, range(cp.num_hidden_layers), False, x3,
-                                          [Group(0, B, Lp, None, B)], False, X32=f32(x3))
-        prop_embeds_m_32 = self.last32 if r32 else None
+        prop_embeds_m, _, prop_embeds_m_32 = self.stack_fwd("property_encoder_m.", cp, range(cp.num_hidden_layers), False, x3,
+                                                            Batch([Group(0, B, Lp, None, B)]), False, X32=f32(x3))
         self._join(side)
         self._join(side_m)
         if pk:
-            g5 = [Group(0, B, Lt, None, 0, kv=prop_embeds_m, Lkv=Lp, kv_mask=None, q_row0=pk["row0"], q_len=pk["len"], nrows=M)]
+            g5 = Batch([Group(0, B, Lt, None, 0, kv=prop_embeds_m, Lkv=Lp, kv_mask=None, q_row0=pk["row0"], q_len=pk["len"], nrows=M)])
         else:
-            g5 = [Group(0, B, Lt, mask32, 0, kv=prop_embeds_m, Lkv=Lp, kv_mask=None)]
+            g5 = Batch([Group(0, B, Lt, mask32, 0, kv=prop_embeds_m, Lkv=Lp, kv_mask=None)])
         # The teacher's fusion pass (S5: P9b + LM head, small M) is needed only by the LM loss at the very end: it runs on
         # the side stream underneath the features / ITA / S6 work below.
         side5 = self._fork()
         with self._on(side5):
-            y5, _ = self.stack_fwd("text_encoder_m.bert.", ct, range(f, n), True, hidden9, g5, False, X32=hidden9_32)
+            y5, _, _ = self.stack_fwd("text_encoder_m.bert.", ct, range(f, n), True, hidden9, g5, False, X32=hidden9_32)
             logits_m, _ = self.lm_head_fwd("text_encoder_m.", ct, y5, False)
             if pk:                                               # the loss kernel indexes [B, Lt, V]
                 V_ = logits_m.shape[1]
@@ -302,13 +294,13 @@ class PretrainStep(Engine):
                 gt = [Group(4 * B * Lp, 4 * B, Lt, kvmask_qpv, 3 * B).attend(src_pv, torch.cat([ar, neg[:B], ar, ar]))]
                 neg_rows, cls_text, Mn = None, torch.arange(3 * B, dtype=torch.int64, device=self.dev) * Lt, B * Lt
             X6 = torch.cat([qpv, qtext])
-            g6 = [Group(0, 4 * B, Lp, None, 3 * B, kv_mask=kvmask_qpv).attend(src_text, torch.cat([ar, ar, neg[B:], ar]))] + gt
+            g6 = Batch([Group(0, 4 * B, Lp, None, 3 * B, kv_mask=kvmask_qpv).attend(src_text, torch.cat([ar, ar, neg[B:], ar]))] + gt)
             src_text.finalize()
             src_pv.finalize()
-            y6, tape6 = self.stack_fwd("text_encoder.bert.", ct, range(f, n), True, X6, g6, save, X32=torch.cat([qpv_32, qtext_32]) if r32 else None)
+            y6, tape6, y6_32 = self.stack_fwd("text_encoder.bert.", ct, range(f, n), True, X6, g6, save, X32=torch.cat([qpv_32, qtext_32]) if r32 else None)
             ypv, ytext = y6[:4 * B * Lp], y6[4 * B * Lp:]
             # the loss heads read the fp32 twins in that mode (forward and backward: the tape keeps what the forward read)
-            ypv_h, ytext_h = (self.last32[:4 * B * Lp], self.last32[4 * B * Lp:]) if r32 else (ypv, ytext)
+            ypv_h, ytext_h = (y6_32[:4 * B * Lp], y6_32[4 * B * Lp:]) if r32 else (ypv, ytext)
 
             # ---- ITM head (:199-206) on the position-0 rows of the first 3B sequences of both halves
             vl_logits = self._new(3 * B, 2, dtype=torch.float32) if aux is not None else None
@@ -504,6 +496,4 @@ class PretrainStep(Engine):
                       d_w=P.g("property_embed.weight"), d_b=P.g("property_embed.bias"), d_cls=P.g("property_cls"),
                       d_masktok=P.g("property_mask"))
         self._join(side)
-        self.wgrad_join(release=True)                           # the weight gradients of the side stream are complete from here on
-        self._wg_pending = False
-        self.tape = None
+        self.end_backward()

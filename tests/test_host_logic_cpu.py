@@ -98,6 +98,80 @@ def test_step_schedule_dry_run(dry):
     assert len(out) == 4
 
 
+# C entries whose launches run over a batch's rows and may take the row count from device memory: name -> (argument index of the
+# count, argument index of the leading dimension it replaces) in include/spmm_hip.h
+_ROW_COUNT_ARGS = {"spmm_gemm_nt": (22, 4), "spmm_gemm_tn": (13, 4), "spmm_ln_fwd": (14, 8), "spmm_ln_bwd": (17, 10), "spmm_colsum_bf16": (5, 2)}
+
+
+def _record_row_counts(dry, monkeypatch):
+    """Wraps ops._call: -> list of (C entry, leading dimension, address of the device-side row count or None), filled as launches are made."""
+    seen, orig = [], dry._call
+
+    def call(name, *args):
+        if name in _ROW_COUNT_ARGS:
+            i_dev, i_m = _ROW_COUNT_ARGS[name]
+            seen.append((name, args[i_m], None if args[i_dev] is None else args[i_dev].value))
+        return orig(name, *args)
+
+    monkeypatch.setattr(dry, "_call", call)
+    return seen
+
+
+def _three_layer_model():
+    """The tiny model with TWO fusion layers: the fusion batch of the packed path then has layers below its CLS-only top layer, the
+    ones that run on the batch whose row count only the device knows (tiny_config() alone has none)."""
+    from dataclasses import replace
+    from spmm_amd.config import tiny_config
+    from spmm_amd.model import SPMM
+    sched = {'sched': 'cosine', 'lr': 5e-5, 'epochs': 30, 'min_lr': 1e-5, 'decay_rate': 1, 'warmup_lr': 5e-5, 'warmup_epochs': 20,
+             'cooldown_epochs': 0}
+    tc = {'embed_dim': 64, 'temp': 0.07, 'queue_size': 16, 'momentum': 0.995, 'alpha': 0.4, 'schedular': sched,
+          'optimizer': {'opt': 'adamW', 'lr': 5e-5, 'weight_decay': 0.02}}
+    cfg = tiny_config()
+    return SPMM(config=tc, spmm_config=replace(cfg, text=replace(cfg.text, num_hidden_layers=3)), loader_len=4).train()
+
+
+def test_device_row_counts_travel_with_the_batch(dry, monkeypatch):
+    """Which launches read their row count from device memory is a property of the batch they run over (engine.Batch.rows_dev), not of a
+    tensor's shape."""
+    from spmm_amd.engine import Batch
+    m = _three_layer_model()
+    eng, ct = m.engine, m.engine.cfg.text
+    seen = _record_row_counts(dry, monkeypatch)
+    captured, s6_forward = {}, eng._s6_forward_cls
+    monkeypatch.setattr(eng, "_s6_forward_cls", lambda *a, **k: captured.setdefault("S6", s6_forward(*a, **k)))
+    B, Lt, Lp = 4, 16, eng.cfg.n_props + 1
+    prop, ids, mask = O.synthetic_batch(B, Lt, seed=7)
+    M = int(mask.sum())
+    Rcap = 4 * B * Lp + 2 * M + 2 * B * Lt
+    assert (M, Rcap) == (56, 1104)
+    m.training_step((prop, (ids, mask)), batch_idx=0)
+    S6 = captured["S6"]                                          # (holds the plan's tensors: their addresses stay theirs for the whole test)
+    g_lo = S6["g_lo"]
+    rows_dev, mn_dev = S6["fp"]["rows_dev"].data_ptr(), S6["fp"]["mn_dev"].data_ptr()
+    assert g_lo.rows_dev.data_ptr() == rows_dev and S6["g_top"].rows_dev is None
+    # 1. the packed step: a device-side count on exactly two sets of launches -- those over the fusion batch's Rcap rows (one pointer) and
+    #    the SelfKV ones over the packed text negatives (B*Lt rows allocated, another pointer) -- and on nothing else
+    with_count = [(n, rows, p) for n, rows, p in seen if p is not None]
+    assert {p for _, rows, p in with_count if rows == Rcap} == {rows_dev}
+    assert {(rows, p) for _, rows, p in with_count if rows != Rcap} == {(B * Lt, mn_dev)}
+    assert not [n for n, rows, p in seen if rows == Rcap and p is None]
+    by_entry = lambda rows: {n: sum(1 for n_, r_, _ in with_count if n_ == n and r_ == rows) for n in _ROW_COUNT_ARGS}
+    assert by_entry(Rcap) == {"spmm_gemm_nt": 12, "spmm_gemm_tn": 6, "spmm_colsum_bf16": 2, "spmm_ln_fwd": 3, "spmm_ln_bwd": 3}
+    assert by_entry(B * Lt) == {"spmm_gemm_nt": 2, "spmm_gemm_tn": 1, "spmm_colsum_bf16": 1, "spmm_ln_fwd": 0, "spmm_ln_bwd": 0}
+    # 2. what a shape match cannot express: the same input tensor and the same groups, with a device-side row count and without
+    X = torch.zeros(Rcap, ct.hidden_size, dtype=torch.bfloat16)
+    f, n = ct.fusion_layer, ct.num_hidden_layers
+    for batch, want in ((Batch(g_lo.groups, rows_dev=g_lo.rows_dev), {rows_dev}), (Batch(g_lo.groups), {None})):
+        seen.clear()
+        y, tape, _ = eng.stack_fwd("text_encoder.bert.", ct, range(f, n - 1), True, X, batch, True)
+        dkv = {id(S6["src_text"]): torch.zeros(M, ct.hidden_size), id(S6["src_pv"]): torch.zeros(B * Lp, ct.hidden_size)}
+        eng.stack_bwd("text_encoder.bert.", ct, range(f, n - 1), tape, torch.zeros_like(y), batch, dkv_acc=dkv)
+        over_batch = [p for _, rows, p in seen if rows == Rcap]
+        assert len(over_batch) == 26 and set(over_batch) == want
+        assert {p for _, rows, p in seen if rows != Rcap} == {None}      # (the shared key/value sources' projections and gradients)
+
+
 def test_cosine_schedule_matches_oracle_table():
     from spmm_amd.model import _CosineSchedule
     for sc in ({'lr': 5e-5, 'epochs': 30, 'min_lr': 1e-5, 'warmup_lr': 5e-5, 'warmup_epochs': 20},

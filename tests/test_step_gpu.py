@@ -217,6 +217,27 @@ def test_fused_cross_attention_self_check_falls_back_to_the_composite(env, monke
                 out[mode] = np.array([float(x) for x in m(prop, ids, mask, alpha=0.4, mpm_mask=mpm.cuda(), neg_idx=tuple(_cuda(*neg)))])
     print("composite", out["off"], "after the fallback", out["broken"])
     np.testing.assert_allclose(out["broken"], out["off"], rtol=1e-5, atol=1e-6)       # (eval mode: no dropout, the composite is deterministic but for atomic sums)
+    # Second round, train mode (dropout on, taped forwards, the one-launch form asked for in EVERY block): the composite launches that
+    # replace the failed form run with the salts already drawn for that block, so from the block that fell back on the process draws the
+    # masks of a fused_xattn="off" process -- the losses of this and of the next forward are the composite's.
+    tr = {}
+    for mode in ("off", "broken"):
+        m = SPMM(config=None, spmm_config=cfg, options=EngineOptions.from_env(fused_xattn="off" if mode == "off" else "all"))
+        m.load_state_dict({k: v.detach().clone() for k, v in sd.items()})
+        m.train()
+        m.engine.seed.fill_(777)
+        steps = []
+        for k in range(2):
+            if mode == "broken" and k == 0:
+                with pytest.warns(UserWarning, match="falling back to the composite"):
+                    l = m(prop, ids, mask, alpha=0.4, mpm_mask=mpm.cuda(), neg_idx=tuple(_cuda(*neg)))
+            else:
+                l = m(prop, ids, mask, alpha=0.4, mpm_mask=mpm.cuda(), neg_idx=tuple(_cuda(*neg)))
+            steps.append([float(x.detach()) for x in l])
+        tr[mode] = np.array(steps)
+    assert m.engine._xattn_off
+    print("train mode: composite", tr["off"], "after the fallback", tr["broken"])
+    np.testing.assert_allclose(tr["broken"], tr["off"], rtol=1e-5, atol=1e-6)
 
 
 def test_fused_cross_attention_inside_the_step(env):
