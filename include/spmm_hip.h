@@ -269,7 +269,8 @@ int spmm_ita_rows(const float* S, const float* SM, long ldj, int nrows, int B, i
 /* hard negatives SPMM_models.py:154-178: one multinomial draw per row, on device. */
 int spmm_sample_neg(const float* S, long ldj, int B, const long* forced, const uint64_t* seed_ptr, uint64_t salt, long* out,
                     long out_offset, spmm_stream_t stream);
-/* next-token CE + distillation SPMM_models.py:233-238 and its gradient w.r.t. the student logits. */
+/* next-token CE + distillation SPMM_models.py:233-238 and its gradient w.r.t. the student logits.  n_nonpad_ws: 4 ints, 8-byte aligned
+ * (the count of non-PAD labels, then the ticket and the 64-bit fixed-point sum of the order-independent loss accumulation). */
 int spmm_lm_loss(const float* logits, const float* logits_m, long ldl, const int* ids, long nseq, int L, int V,
                  const float* alpha_ptr, int* n_nonpad_ws, const float* gscale, void* dlogits, long ldd, int Vpad,
                  float* losses, int loss_slot, spmm_stream_t stream);
@@ -286,7 +287,7 @@ int spmm_itm_head(const void* xa, long stride_a, const void* xb, long stride_b, 
 int spmm_task_head(const void* A, long lda, int B, int W, const float* W2, const float* b2, int C, int kind, const void* target,
                    const float* gscale, float* logits, float* loss, void* dA, long ldda, float* dW2, float* db2, int do_bwd,
                    spmm_stream_t stream);
-/* property_mtr_head final Linear(H,1) + masked MSE * 5 SPMM_models.py:251-256. */
+/* property_mtr_head final Linear(H,1) + masked MSE * 5 SPMM_models.py:251-256.  n_keep_ws: 4 ints, 8-byte aligned (as n_nonpad_ws). */
 int spmm_mpm_head(const void* h, int Lp, int H, const float* w, const float* bias, const float* target, const float* mask,
                   int B, int* n_keep_ws, const float* gscale, float* losses, int loss_slot, float* pred_out, void* dh,
                   float* dw, float* db, int do_bwd, int x_is_f32, spmm_stream_t stream);

@@ -32,6 +32,25 @@ __device__ __forceinline__ float block_max(float v, float* sh) {
   return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
 }
 
+// Order-independent sum of the per-workgroup loss partials of one launch (lm_loss, mpm_head: up to 1024 workgroups).  One fp32 atomic
+// per workgroup onto losses[slot] rounds every partial at the magnitude of the running total, in the order the workgroups happen to
+// arrive: measured 14 ulp of spread between launches on the same input (4224 rows).  Instead every workgroup adds its partial as
+// 2^-40 fixed point into a 64-bit integer (integer addition is associative and here exact to 1e-12 per term), and the last workgroup
+// to arrive adds the total to losses[slot] with ONE fp32 atomic.  ws = {count of the launch before, ticket, 64-bit sum}: ws[1..3] are
+// zeroed by the counting kernel that precedes the launch on the stream.  A partial that is not finite (the NaN guard must see it) or
+// too large for the fixed point goes to losses[slot] directly.
+__device__ __forceinline__ void loss_partial_add(float partial, int* __restrict__ ws, float* __restrict__ dst) {   // one thread per workgroup
+  unsigned long long* acc = (unsigned long long*)(ws + 2);
+  if (fabsf(partial) < 4096.f) atomicAdd(acc, (unsigned long long)__double2ll_rn((double)partial * 1099511627776.0));
+  else atomicAdd(dst, partial);
+  __threadfence();
+  if (atomicAdd(ws + 1, 1) == (int)gridDim.x - 1) {
+    __threadfence();
+    const long long tot = (long long)atomicAdd(acc, 0ull);
+    atomicAdd(dst, (float)((double)tot * (1.0 / 1099511627776.0)));
+  }
+}
+
 // ---------------------------------------------------------------- l2 normalise (one wave per row)
 // y = x / max(||x||, 1e-12); optionally emit the split-bf16 GEMM operand row [hi | lo | hi] (a3, for the A side)
 // or [hi | hi | lo] (w3, for the W side) so that a3 . w3 = hi*hi + lo*hi + hi*lo ~ fp32 product.
@@ -208,13 +227,14 @@ __global__ __launch_bounds__(1024) void count_nonpad_kernel(const int* __restric
     float t = 0.f;
     for (int w = 0; w < 16; ++w) t += sh[w];
     *out = (int)(t + 0.5f);
+    out[1] = out[2] = out[3] = 0;                      // ticket and fixed-point sum of loss_partial_add
   }
 }
 // One wave per row, workgroups stride over the rows and add ONE loss atomic each: 16 384 same-address atomics (one per row) serialise
 // at ~13 ns apiece -- 213 us of a 215-us launch, measured.
 __global__ __launch_bounds__(256) void lm_loss_kernel(const float* __restrict__ logits, const float* __restrict__ logits_m, long ldl,
                                const int* __restrict__ ids, long nseq, int L, int V, const float* __restrict__ alpha_ptr,
-                               const int* __restrict__ n_nonpad, const float* __restrict__ gscale, bf16* __restrict__ dlogits,
+                               int* __restrict__ n_nonpad, const float* __restrict__ gscale, bf16* __restrict__ dlogits,
                                long ldd, int Vpad, float* __restrict__ losses, int loss_slot) {
   __shared__ float sh[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -262,7 +282,7 @@ __global__ __launch_bounds__(256) void lm_loss_kernel(const float* __restrict__ 
   }
   if (lane == 0) sh[wave] = lacc;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(losses + loss_slot, (sh[0] + sh[1]) + (sh[2] + sh[3]));
+  if (threadIdx.x == 0) loss_partial_add((sh[0] + sh[1]) + (sh[2] + sh[3]), n_nonpad, losses + loss_slot);
 }
 
 // ---------------------------------------------------------------- ITM head fwd+bwd (one wave per pair row)
@@ -320,13 +340,13 @@ __global__ void count_keep_kernel(const float* __restrict__ mask, long n, int* _
   float c = 0.f;
   for (long i = threadIdx.x; i < n; i += 256) c += (mask[i] == 0.f) ? 1.f : 0.f;
   c = block_sum(c, sh);
-  if (threadIdx.x == 0) *out = (int)(c + 0.5f);
+  if (threadIdx.x == 0) { *out = (int)(c + 0.5f); out[1] = out[2] = out[3] = 0; }   // (ticket and fixed-point sum of loss_partial_add)
 }
 // Workgroups stride over the rows; the loss, db and the H columns of dw are accumulated per wave in registers and leave as one
 // atomic per workgroup (per column): one atomic per ROW on the same addresses serialised the launch (~13 ns each).
 template <typename TX>
 __global__ __launch_bounds__(256) void mpm_head_kernel(const TX* __restrict__ h, int Lp, int H, const float* __restrict__ w, const float* __restrict__ bias,
-                                const float* __restrict__ target, const float* __restrict__ mask, int B, const int* __restrict__ n_keep,
+                                const float* __restrict__ target, const float* __restrict__ mask, int B, int* __restrict__ n_keep,
                                 const float* __restrict__ gscale, float* __restrict__ losses, int loss_slot, float* __restrict__ pred_out,
                                 bf16* __restrict__ dh, float* __restrict__ dw, float* __restrict__ db, int do_bwd) {
   constexpr int MAXC = 16;                               // H <= 1024
@@ -371,7 +391,7 @@ __global__ __launch_bounds__(256) void mpm_head_kernel(const TX* __restrict__ h,
   if (lane == 0) { red[wave][1024] = lacc; red[wave][1025] = dbacc; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    atomicAdd(losses + loss_slot, (red[0][1024] + red[1][1024]) + (red[2][1024] + red[3][1024]));
+    loss_partial_add((red[0][1024] + red[1][1024]) + (red[2][1024] + red[3][1024]), n_keep, losses + loss_slot);
     if (do_bwd) atomicAdd(db, (red[0][1025] + red[1][1025]) + (red[2][1025] + red[3][1025]));
   }
   if (do_bwd)
@@ -489,6 +509,7 @@ extern "C" int spmm_lm_loss(const float* logits, const float* logits_m, long ldl
                             const float* alpha_ptr, int* n_nonpad_ws, const float* gscale, void* dlogits, long ldd, int Vpad,
                             float* losses, int loss_slot, hipStream_t stream) {
   SPMM_CHECK_SHAPE(nseq > 0 && L > 1 && V > 0 && Vpad >= V, "spmm_lm_loss: nseq=%ld L=%d V=%d Vpad=%d", nseq, L, V, Vpad);
+  SPMM_CHECK_SHAPE(n_nonpad_ws && (uintptr_t)n_nonpad_ws % 8 == 0, "spmm_lm_loss: the workspace is 4 ints, 8-byte aligned");
   hipLaunchKernelGGL(count_nonpad_kernel, dim3(1), dim3(1024), 0, stream, ids, nseq, L, n_nonpad_ws);
   hipLaunchKernelGGL(lm_loss_kernel, dim3((nseq * L + 3) / 4 < 1024 ? (nseq * L + 3) / 4 : 1024), dim3(256), 0, stream, logits, logits_m, ldl, ids, nseq, L, V, alpha_ptr,
                      n_nonpad_ws, gscale, (bf16*)dlogits, ldd, Vpad, losses, loss_slot);
@@ -514,6 +535,7 @@ extern "C" int spmm_mpm_head(const void* h, int Lp, int H, const float* w, const
                              float* dw, float* db, int do_bwd, int x_is_f32, hipStream_t stream) {
   SPMM_CHECK_SHAPE(B > 0 && Lp > 1 && H > 0 && H <= 1024, "spmm_mpm_head: B=%d Lp=%d H=%d (H <= 1024)", B, Lp, H);
   SPMM_CHECK_SHAPE(!do_bwd || (dh && dw && db), "spmm_mpm_head: backward outputs missing");
+  SPMM_CHECK_SHAPE(n_keep_ws && (uintptr_t)n_keep_ws % 8 == 0, "spmm_mpm_head: the workspace is 4 ints, 8-byte aligned");
   hipLaunchKernelGGL(count_keep_kernel, dim3(1), dim3(256), 0, stream, mask, (long)B * (Lp - 1), n_keep_ws);
   const dim3 mgrid((B * Lp + 3) / 4 < 512 ? (B * Lp + 3) / 4 : 512);
   if (x_is_f32)

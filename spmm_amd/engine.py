@@ -171,7 +171,7 @@ class Engine:
         self.seed_rank_offset = rank * 0x9E3779B97F4A7C15 % (1 << 62)      # (checkpoints hold the rank-independent part: model.py)
         self.seed = torch.full((1,), (0x5DEECE66D + self.seed_rank_offset) % (1 << 62), dtype=torch.int64, device=device)
         self.nan_flag = self.step_zero[9:10]
-        self.icount = torch.zeros(4, dtype=torch.int32, device=device)
+        self.icount = torch.zeros(8, dtype=torch.int32, device=device)      # two 4-int workspaces: lm_loss, mpm_head
         self.dtemp_ita = self.step_zero[8:9].view(torch.float32)
         self.train_mode = True
         self.hint_bad = self.step_zero[10:11]              # a caller's token-count hint contradicted the mask (step.py)

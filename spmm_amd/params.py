@@ -6,6 +6,7 @@ read them as one [3H,H] matrix without copies."""
 from __future__ import annotations
 
 import math
+import struct
 from typing import Dict, List, Optional
 
 import torch
@@ -14,6 +15,19 @@ from . import ops
 from .config import SPMMConfig, is_buffer, momentum_twin, state_spec, student_of
 
 ALIGN = 64   # elements; keeps every tensor 256-B (fp32) / 128-B (bf16) aligned
+
+
+def ct_descriptor_table(pairs):
+    """Descriptor table of ops.cast_transpose_multi (CtDesc of csrc/rowops.hip: fp32 src [R, C], bf16 dstT [C, R], R, C, first tile,
+    tile columns) for (src, dstT) tensor pairs -> (bytes, total number of 64 x 64 tiles = workgroups of the launch)."""
+    blob, tile0 = b"", 0
+    for src, dstT in pairs:
+        R, C = src.shape
+        ntr, ntc = (R + 63) // 64, (C + 63) // 64
+        blob += struct.pack("<QQiiii", src.data_ptr(), dstT.data_ptr(), R, C, tile0, ntc)
+        tile0 += ntr * ntc
+    assert len(blob) == len(pairs) * 32
+    return blob, tile0
 
 
 def _layout_order(spec) -> List[str]:
@@ -181,16 +195,9 @@ class ParamStore:
         if not srcs:
             return
         if getattr(self, "_ct_n", -1) != len(srcs):       # (re)build the device descriptor table when shadows were added
-            import struct
-            blob, tile0 = b"", 0
-            for key, src in srcs.items():
-                R, C = src.shape
-                ntr, ntc = (R + 63) // 64, (C + 63) // 64
-                blob += struct.pack("<QQiiii", src.data_ptr(), self._wT[key].data_ptr(), R, C, tile0, ntc)
-                tile0 += ntr * ntc
-            assert len(blob) == len(srcs) * 32
+            blob, tiles = ct_descriptor_table([(src, self._wT[key]) for key, src in srcs.items()])
             self._ct_desc = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(self.device)
-            self._ct_n, self._ct_tiles = len(srcs), tile0
+            self._ct_n, self._ct_tiles = len(srcs), tiles
         ops.cast_transpose_multi(self._ct_desc, self._ct_n, self._ct_tiles)
 
     def copy_params(self):

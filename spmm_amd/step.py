@@ -325,7 +325,7 @@ class PretrainStep(Engine):
         self._join(side5)
         hid10 = hid10_cls if cls_top else ytext[ytext.shape[0] - B * Lt:]
         logits, lmsv = self.lm_head_fwd("text_encoder.", ct, hid10, save)
-        ops.lm_loss(logits, logits_m, ids32, nseq=B, L=Lt, V=ct.vocab_size, alpha=self.alpha, ws=self.icount[0:1], losses=self.losses,
+        ops.lm_loss(logits, logits_m, ids32, nseq=B, L=Lt, V=ct.vocab_size, alpha=self.alpha, ws=self.icount[0:4], losses=self.losses,
                     slot=LOSS_MLM)
 
         # ---- MPM (:241-256)
@@ -344,7 +344,7 @@ class PretrainStep(Engine):
                        eps=ct.layer_norm_eps)
         pred = self._new(B, cfg.n_props, dtype=torch.float32) if aux is not None else None
         ops.mpm_head(mln_h, Lp, H, P.w("property_mtr_head.3.weight"), P.w("property_mtr_head.3.bias"), prop, mpm_mask, B=B,
-                     ws=self.icount[1:2], losses=self.losses, slot=LOSS_MPM, pred=pred)
+                     ws=self.icount[4:8], losses=self.losses, slot=LOSS_MPM, pred=pred)
 
         if aux is not None:
             aux.update(prop_embeds=prop_embeds, text_embeds=text_embeds, prop_embeds_m=prop_embeds_m, text_embeds_m=text_embeds_m,
@@ -389,7 +389,7 @@ class PretrainStep(Engine):
         # ---- MPM head
         dmln = self._new(B * Lp, H)
         ops.mpm_head(T["mln"], Lp, H, P.w("property_mtr_head.3.weight"), P.w("property_mtr_head.3.bias"), T["prop"], T["mpm_mask"], B=B,
-                     ws=self.icount[1:2], losses=scratch, slot=LOSS_MPM, dh=dmln, dw=P.g("property_mtr_head.3.weight"),
+                     ws=self.icount[4:8], losses=scratch, slot=LOSS_MPM, dh=dmln, dw=P.g("property_mtr_head.3.weight"),
                      db=P.g("property_mtr_head.3.bias"), gscale=gs[1:2])
         dmz = self._new(B * Lp, H)
         ops.ln_bwd(dmln, T["mt"], T["mmean"], T["mrstd"], P.w("property_mtr_head.2.weight"), dmz,
@@ -401,7 +401,7 @@ class PretrainStep(Engine):
         # ---- LM head
         V = ct.vocab_size
         dlogits = self._new(B * Lt, _ceil(V, 64))
-        ops.lm_loss(T["logits"], T["logits_m"], T["ids32"], nseq=B, L=Lt, V=V, alpha=self.alpha, ws=self.icount[0:1], losses=scratch,
+        ops.lm_loss(T["logits"], T["logits_m"], T["ids32"], nseq=B, L=Lt, V=V, alpha=self.alpha, ws=self.icount[0:4], losses=scratch,
                     slot=LOSS_MLM, dlogits=dlogits, gscale=gs[0:1])
         self.lm_head_bwd("text_encoder.", ct, T["lmsv"], dlogits, out=dY_lm)
 

@@ -670,37 +670,7 @@ def test_attention_dropout_consistency(ops, Lq, Lkv):
     assert ((dropped_probabilities() != 0) != (pd != 0)).float().mean().item() > 0.05
 
 
-def _host_dropout_keep(seed, salt, rows, ncols, p):
-    """Host model of csrc/common.h's dropout counter hash: keep[row, col] for `rows` (uint64 row counters) x ncols elements.
-    seed_mix (two splitmix64 rounds over seed and salt) -> drop_rowkey (lowbias32 of the row) -> drop_pair (Weyl step + two 24-bit
-    multiply rounds) -> one 16-bit half per element against round(p * 65536).  The statistics of THIS function were checked against
-    lowbias32 when it was adopted (EXPERIMENTS.md 1.7); the test below pins the kernels to it bit for bit."""
-    M64, M32 = (1 << 64) - 1, np.uint64(0xffffffff)
-
-    def splitmix64(z):
-        z = (z + 0x9E3779B97F4A7C15) & M64
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-        return z ^ (z >> 31)
-
-    def mix32(x):                                   # uint64 arrays holding 32-bit values
-        x = x ^ (x >> np.uint64(16)); x = (x * np.uint64(0x21f0aaad)) & M32
-        x = x ^ (x >> np.uint64(15)); x = (x * np.uint64(0x735a2d97)) & M32
-        return x ^ (x >> np.uint64(15))
-
-    def mix24(x):
-        x = x ^ (x >> np.uint64(16)); x = ((x & np.uint64(0xffffff)) * np.uint64(0xda8f81)) & M32
-        x = x ^ (x >> np.uint64(16)); x = ((x & np.uint64(0xffffff)) * np.uint64(0x76dfb5)) & M32
-        return x ^ (x >> np.uint64(16))
-
-    s64 = splitmix64((splitmix64(seed & M64) + salt) & M64)
-    s_lo, s_hi = np.uint64(s64 & 0xffffffff), np.uint64(s64 >> 32)
-    rows = np.asarray(rows, dtype=np.uint64)
-    rowkey = mix32((rows & M32) ^ s_lo) ^ s_hi ^ (((rows >> np.uint64(32)) * np.uint64(0x9E3779B1)) & M32)
-    pair = np.arange(ncols // 2, dtype=np.uint64)
-    r = mix24((rowkey[:, None] + pair[None, :] * np.uint64(0x9E3779B1)) & M32)
-    u = np.stack([r & np.uint64(0xffff), r >> np.uint64(16)], axis=2).reshape(len(rows), ncols)
-    return u >= np.uint64(int(p * 65536 + 0.5))
+from helpers_gpu import _host_dropout_keep      # noqa: E402  (the host model of the generator lives in tests/helpers_gpu.py)
 
 
 def test_dropout_masks_equal_the_host_model_of_the_hash(ops):
