@@ -630,8 +630,10 @@ def test_attention_backward_near_constant_values(ops):
 
 @pytest.mark.parametrize("Lq,Lkv", [(54, 64), (200, 256)])
 def test_attention_dropout_consistency(ops, Lq, Lkv):
-    """Recover the dropout mask from forwards with V = a shifted identity (64 keys per pass), then check fwd/bwd against torch using
-    THAT mask."""
+    """The dense, unmasked, non-causal self-attention form only: recover the dropout mask from forwards with V = a shifted identity (one
+    pass per 64 keys), then check fwd/bwd against torch using THAT mask.  The layouts the training step launches with dropout on (packed
+    rows, shared sources, causal_from, key masks, Lq = 1, the chunked path) and the mask each backward path applies, decision by
+    decision, are in tests/test_attention_dropout_gpu.py."""
     nseq, nH, p = 3, 2, 0.1
     H = nH * 64
     Q, K = rnd(nseq * Lq, H, seed=40), rnd(nseq * Lkv, H, seed=41)
