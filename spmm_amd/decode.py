@@ -4,6 +4,7 @@ a key/value cache, returning per molecule the hypotheses the reference's one-mol
 restated in oracle/decode_oracle.py -- test infrastructure, the yard-stick of tests/ -- not here."""
 from __future__ import annotations
 
+import functools
 from typing import List, Tuple
 
 import torch
@@ -240,14 +241,6 @@ class CachedDecoder:
         self.N = int(keep.numel())
         self.R = self.N * k
 
-    def _attn_out(self, pf, ctx, resid):
-        ops, P, c = self.ops, self.P, self.c
-        x = self._new(self.R, self.H)
-        ops.gemm_nt(ctx, P.wb(pf + "output.dense.weight"), x, bias=P.w(pf + "output.dense.bias"))
-        y = self._new(self.R, self.H)
-        ops.ln_fwd(x, resid, P.w(pf + "output.LayerNorm.weight"), P.w(pf + "output.LayerNorm.bias"), y, eps=c.layer_norm_eps)
-        return y
-
     @torch.no_grad()
     def step(self, ids: torch.Tensor, t: int, t_dev: torch.Tensor | None = None) -> torch.Tensor:
         """ids [R]: the token at position t of every beam -> fp32 logits [R, V] for position t + 1.
@@ -255,6 +248,8 @@ class CachedDecoder:
         launch sequence independent of the step -- capturable once as a hipGraph and replayed (beam_search_batched(graph=True))."""
         ops, P, c, R, H, nH = self.ops, self.P, self.c, self.R, self.H, self.c.num_attention_heads
         bp = self.pfx + "bert."
+        # residual sublayers: the engine's (inference: no tape, dropout off -- the row kernel then never reads the seed)
+        sub = functools.partial(self.eng._proj_ln, X32=None, save=False, eps=c.layer_norm_eps, ph=0.0, salt=0)
         x = self._new(R, H)
         ops.embed_step_ln_fwd(ids.to(torch.int32).contiguous(), t, x, pos_ptr=t_dev, word=P.w(bp + "embeddings.word_embeddings.weight"),
                               pos=P.w(bp + "embeddings.position_embeddings.weight"), type0=P.w(bp + "embeddings.token_type_embeddings.weight"),
@@ -269,20 +264,17 @@ class CachedDecoder:
             ops.decode_attn(QKV[:, :H], self.kc[l], self.vc[l], ctx, nH=nH, Lkv=self.Lmax if t_dev is not None else t + 1,
                             seq_stride=self.Lmax * H, tok_stride=64, head_stride=self.Lmax * 64, anc=self.anc, group=self.k, t_ptr=t_dev, knew=QKV[:, H:2 * H], vnew=QKV[:, 2 * H:],
                             rowmap=self.rowmap)
-            a = self._attn_out(pf, ctx, x)
+            a = sub(pf + "output.", ctx, x)[0]
             if l >= c.fusion_layer:
                 pf = lp + "crossattention."
                 q = self._new(R, H)
                 ops.gemm_nt(a, P.wb(pf + "self.query.weight"), q, bias=P.w(pf + "self.query.bias"))
                 KV = self.xkv[l]
                 ops.decode_attn(q, KV[:, :H], KV[:, H:], ctx, nH=nH, Lkv=self.Lp, seq_stride=self.Lp * 2 * H, tok_stride=2 * H, kv_div=self.k, group=self.k)
-                a = self._attn_out(pf, ctx, a)
+                a = sub(pf + "output.", ctx, a)[0]
             h = self._new(R, c.intermediate_size)
             ops.gemm_nt(a, P.wb(lp + "intermediate.dense.weight"), h, bias=P.w(lp + "intermediate.dense.bias"), epi=ops.EPI_GELU)
-            x2 = self._new(R, H)
-            ops.gemm_nt(h, P.wb(lp + "output.dense.weight"), x2, bias=P.w(lp + "output.dense.bias"))
-            x = self._new(R, H)
-            ops.ln_fwd(x2, a, P.w(lp + "output.LayerNorm.weight"), P.w(lp + "output.LayerNorm.bias"), x, eps=c.layer_norm_eps)
+            x = sub(lp + "output.", h, a)[0]
         logits, _ = self.eng.lm_head_fwd(self.pfx, c, x, False)
         return logits
 

@@ -146,6 +146,27 @@ class Batch:
         return len(self.groups)
 
 
+@dataclass
+class LnTape:
+    """What the backward of one LayerNorm needs, whichever forward ran it (composite or fused residual sublayer, embeddings, transform heads):
+    the pre-norm sum z (None: the normalised values come from the output y, EngineOptions.ln_from_y), row statistics, dropout salt."""
+    z: Optional[torch.Tensor]
+    y: Optional[torch.Tensor]
+    mean: Optional[torch.Tensor]
+    rstd: Optional[torch.Tensor]
+    salt: int = 0
+
+
+@dataclass
+class HeadTape:
+    """Engine._transform_fwd: parameter names of the dense layer and the LayerNorm, input, GELU pre-activation, the LayerNorm's record."""
+    dense: str
+    norm: str
+    X: torch.Tensor
+    pre: Optional[torch.Tensor]
+    ln: LnTape
+
+
 STREAM_TOKENS_MAX = 49152         # B x Lt above which the step runs on one stream (Engine._one_stream)
 
 
@@ -211,16 +232,12 @@ class Engine:
         if not self.multi_stream or self._one_stream or self.dev.type != "cuda" or ops._DRY_RUN:
             return None
         side = streams.get(self.dev, "side0" if self._one_side else f"side{which}")        # process-wide: every model of a process shares the same streams
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        side.wait_event(ev)
+        streams.after(side, torch.cuda.current_stream())
         return side
 
     def _join(self, side):
         if side is not None:
-            ev = torch.cuda.Event()
-            ev.record(side)
-            torch.cuda.current_stream().wait_event(ev)
+            streams.after(torch.cuda.current_stream(), side)
 
     @staticmethod
     def _on(side):
@@ -228,6 +245,10 @@ class Engine:
 
     def _new(self, *shape, dtype=BF):
         return torch.empty(*shape, dtype=dtype, device=self.dev)
+
+    def _stats(self, M, save):
+        """-> (mean, rstd) fp32 [M] of a LayerNorm whose backward will run, (None, None) otherwise."""
+        return (self._new(M, dtype=torch.float32), self._new(M, dtype=torch.float32)) if save else (None, None)
 
     def _zeros(self, *shape, dtype=BF):
         return ops.zero_(torch.empty(*shape, dtype=dtype, device=self.dev))
@@ -258,9 +279,7 @@ class Engine:
                 ops.colsum_bf16(dY, gb, R_dev=md)
             ops.gemm_tn(dY, X, C, M_dev=md)
             return
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        ws.wait_event(ev)
+        streams.after(ws, torch.cuda.current_stream())
         with torch.cuda.stream(ws):
             if gb is not None:
                 ops.colsum_bf16(dY, gb, R_dev=md)
@@ -285,13 +304,10 @@ class Engine:
         if ws is None or torch.cuda.is_current_stream_capturing():
             fn()
             return
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        ws.wait_event(ev)
+        streams.after(ws, torch.cuda.current_stream())
         with torch.cuda.stream(ws):
             fn()
-            self._pre_bwd = torch.cuda.Event()
-            self._pre_bwd.record(ws)
+            self._pre_bwd = streams.mark(ws)
 
     def pre_backward_wait(self):
         ev, self._pre_bwd = self._pre_bwd, None
@@ -301,9 +317,7 @@ class Engine:
     def wgrad_join(self, release: bool = False):
         """The current stream waits for every weight-gradient launch issued so far."""
         if self._wg_stream is not None and self._wg_pending:
-            ev = torch.cuda.Event()
-            ev.record(self._wg_stream)
-            torch.cuda.current_stream().wait_event(ev)
+            streams.after(torch.cuda.current_stream(), self._wg_stream)
             if release:                               # the current stream is now ordered behind every use: the blocks may go back to it
                 self._wg_keep.clear()
                 self._wg_pending = False
@@ -352,22 +366,38 @@ class Engine:
         ops.ln_fwd_r32(x, X32, gamma, beta, y, y32=y32, **kw)
         return y32
 
-    def _proj_ln(self, A, Wb, bias, resid, X32, gamma, beta, *, save, eps, ph, salt, md=None):
-        """y = LayerNorm(dropout(A W^T + b) + resid): BertSelfOutput / BertOutput (xbert.py:369-373, 447-451): the projection GEMM, then
-        dropout + residual + LayerNorm in one row kernel (the pre-norm sum z is formed in fp32 registers; its bf16 copy is kept for the
-        backward, which regenerates the dropout mask from (seed, salt)).  md: device-side row count of A.  -> (y, z, mean, rstd, y32)"""
+    def _proj_ln(self, op, A, resid, X32, *, save, eps, ph, salt, md=None):
+        """y = LayerNorm(dropout(A W^T + b) + resid): BertSelfOutput / BertOutput (xbert.py:369-373, 447-451) with the parameters
+        `op`dense.* / `op`LayerNorm.*: the projection GEMM, then dropout + residual + LayerNorm in one row kernel (the pre-norm sum z is
+        formed in fp32 registers; its bf16 copy is kept for the backward, which regenerates the dropout mask from (seed, salt)).
+        md: device-side row count of A.  -> (y, LnTape, fp32 twin of y or None); `_proj_ln_bwd` is the backward."""
+        P = self.P
+        Wb = P.wb(op + "dense.weight")
         M, H = A.shape[0], Wb.shape[0]
         x, y = self._new(M, H), self._new(M, H)
-        mean = self._new(M, dtype=torch.float32) if save else None
-        rstd = self._new(M, dtype=torch.float32) if save else None
-        ops.gemm_nt(A, Wb, x, bias=bias, M_dev=md)
+        mean, rstd = self._stats(M, save)
+        ops.gemm_nt(A, Wb, x, bias=P.w(op + "dense.bias"), M_dev=md)
         # The backward recovers the normalised values from the OUTPUT y (spmm_ln_bwd, beta_from_y): the pre-norm sum is not stored -- one
         # write pass per residual LayerNorm less, and the projection's output buffer is free again at once (EngineOptions.ln_from_y;
         # the fp32 residual stream keeps the stored sum)
         from_y = self.opt.ln_from_y and X32 is None
-        y32 = self._ln_res(x, resid, X32, gamma, beta, y, md, zout=x if (save and not from_y) else None, mean=mean, rstd=rstd, eps=eps,
-                           dropout_p=ph, seed=self.seed, salt=salt)
-        return y, (None if from_y else x), mean, rstd, y32
+        y32 = self._ln_res(x, resid, X32, P.w(op + "LayerNorm.weight"), P.w(op + "LayerNorm.bias"), y, md,
+                           zout=x if (save and not from_y) else None, mean=mean, rstd=rstd, eps=eps, dropout_p=ph, seed=self.seed, salt=salt)
+        return y, LnTape(None if from_y else x, y, mean, rstd, salt), y32
+
+    def _proj_ln_bwd(self, op, tape, dY, A, ph, md=None):
+        """Backward of `_proj_ln` (or of the fused cross-attention launch, which fills the same record) up to the projection's output:
+        -> (dz, dx) = gradient of the residual branch, gradient of the projection's output (one tensor when hidden dropout is off).  The
+        LayerNorm, projection-bias and projection-weight gradients are accumulated; the data-gradient GEMM on dx stays with the caller."""
+        P, (M, H) = self.P, dY.shape
+        dz = self._new(M, H)
+        dx = self._new(M, H) if ph > 0 else dz
+        from_y = tape.z is None                           # (the forward kept no pre-norm sum: normalised values from the output, _proj_ln)
+        ops.ln_bwd(dY, tape.y if from_y else tape.z, tape.mean, tape.rstd, P.w(op + "LayerNorm.weight"), dz, dx=dx if ph > 0 else None,
+                   dgamma=P.g(op + "LayerNorm.weight"), dbeta=P.g(op + "LayerNorm.bias"), dropout_p=ph, seed=self.seed, salt=tape.salt,
+                   dxsum=P.g(op + "dense.bias"), rows_dev=md, beta_from_y=P.w(op + "LayerNorm.bias") if from_y else None)
+        self._wgrad(dx, A, P.g(op + "dense.weight"), md=md)
+        return dz, dx
 
     def _attn_block_fwd(self, pfx, c, X, groups, save, cross, X32=None):
         """BertAttention.forward xbert.py:401-422 on a token batch.  cross=True uses the groups' key/value sources.
@@ -377,7 +407,7 @@ class Engine:
         # launches, the fused one-launch form and the composite that replaces a fused form that failed its self-check draw the same masks
         salts_a = [self._next_salt() for _ in groups]
         salt_h = self._next_salt()
-        sv = {"X": X, "salt_a": salts_a, "salt_h": salt_h, "cross": cross}
+        sv = {"X": X, "salt_a": salts_a, "cross": cross}
         if not cross:
             ctx, core = self._self_attn_fwd(pfx, c, X, groups, save, salts_a)
         else:
@@ -408,10 +438,9 @@ class Engine:
                     sv.update(out)
                     return y, (sv if save else None), None
             ctx, core = self._xattn_core_fwd(c, Qc, kv_of, groups, save, salts_a)
-        y, z, mean, rstd, y32 = self._proj_ln(ctx, P.wb(pfx + ".output.dense.weight"), P.w(pfx + ".output.dense.bias"), X, X32,
-                                              P.w(pfx + ".output.LayerNorm.weight"), P.w(pfx + ".output.LayerNorm.bias"), save=save,
-                                              eps=c.layer_norm_eps, ph=self._p_hidden(c), salt=salt_h, md=groups.rows_dev)
-        sv.update(core, ctx=ctx, z=z, y=y, mean=mean, rstd=rstd)
+        y, ln, y32 = self._proj_ln(pfx + ".output.", ctx, X, X32, save=save, eps=c.layer_norm_eps, ph=self._p_hidden(c), salt=salt_h,
+                                   md=groups.rows_dev)
+        sv.update(core, ctx=ctx, ln=ln)
         return y, (sv if save else None), y32
 
     def _self_attn_fwd(self, pfx, c, X, groups, save, salts):
@@ -469,8 +498,7 @@ class Engine:
         P, H, nH, M = self.P, c.hidden_size, c.num_attention_heads, X.shape[0]
         y = self._new(M, H)
         z, ctx = (self._new(M, H), self._new(M, H)) if save else (None, None)
-        mean = self._new(M, dtype=torch.float32) if save else None
-        rstd = self._new(M, dtype=torch.float32) if save else None
+        mean, rstd = self._stats(M, save)
         WoF = P.wF(pfx + ".output.dense.weight")
         KVs, lses = [], []
         for g, salt in zip(groups, salts):
@@ -485,20 +513,18 @@ class Engine:
                           row_base=r.start, **g.cross_layout())
             KVs.append(KV)
             lses.append(lse)
-        return y, dict(KV=KVs, lse=lses, ctx=ctx, z=z, y=y, mean=mean, rstd=rstd)
+        return y, dict(KV=KVs, lse=lses, ctx=ctx, ln=LnTape(z, y, mean, rstd, salt_h))
 
     def _xattn_agrees(self, pfx, c, X, Qc, KV, g, y, salt_a, salt_h):
         """One-time self-check of the fused kernel: its output `y` on the rows of group g (the batch's first rows) against the composite
         launches with the same dropout masks (same seed, salts and row counter).  The kernel keeps asynchronously loaded registers in
         flight behind hand-counted waits: a compiler change that broke that would corrupt y silently.  A host read.
         -> (agrees, max |dy|, mean |dy|)"""
-        P, H, r = self.P, c.hidden_size, g.rows
-        c2, x2, y2 = self._new(r.stop, H), self._new(r.stop, H), self._new(r.stop, H)
+        H, r = c.hidden_size, g.rows
+        c2 = self._new(r.stop, H)
         ops.attn_fwd_long(Qc[r], KV[:, :H], KV[:, H:], c2, None, nseq=g.nseq, nH=c.num_attention_heads, Lq=g.L, Lkv=g.Lkv, is_cross=True,
                           dropout_p=self._p_attn(c), seed=self.seed, salt=salt_a, **g.cross_layout())
-        ops.gemm_nt(c2, P.wb(pfx + ".output.dense.weight"), x2, bias=P.w(pfx + ".output.dense.bias"))
-        ops.ln_fwd(x2, X[r], P.w(pfx + ".output.LayerNorm.weight"), P.w(pfx + ".output.LayerNorm.bias"), y2,
-                   eps=c.layer_norm_eps, dropout_p=self._p_hidden(c), seed=self.seed, salt=salt_h)
+        y2, _, _ = self._proj_ln(pfx + ".output.", c2, X[r], None, save=False, eps=c.layer_norm_eps, ph=self._p_hidden(c), salt=salt_h)
         d = (y[r].float() - y2.float()).abs()
         dmax, dmean = float(d.max()), float(d.mean())
         scale = max(1.0, float(y2.float().abs().max()) / 8.0)              # (outlier channels of a trained model scale the roundings)
@@ -510,14 +536,7 @@ class Engine:
         P, H, nH = self.P, c.hidden_size, c.num_attention_heads
         X, M, md = sv["X"], sv["X"].shape[0], groups.rows_dev
         pa, ph = self._p_attn(c), self._p_hidden(c)
-        dz = self._new(M, H)
-        dx = self._new(M, H) if ph > 0 else dz
-        from_y = sv["z"] is None                          # (the forward kept no pre-norm sum: normalised values from the output, _proj_ln)
-        ops.ln_bwd(dY, sv["y"] if from_y else sv["z"], sv["mean"], sv["rstd"], P.w(pfx + ".output.LayerNorm.weight"), dz, dx=dx if ph > 0 else None,
-                   dgamma=P.g(pfx + ".output.LayerNorm.weight"), dbeta=P.g(pfx + ".output.LayerNorm.bias"), dropout_p=ph,
-                   seed=self.seed, salt=sv["salt_h"], dxsum=P.g(pfx + ".output.dense.bias"), rows_dev=md,
-                   beta_from_y=P.w(pfx + ".output.LayerNorm.bias") if from_y else None)
-        self._wgrad(dx, sv["ctx"], P.g(pfx + ".output.dense.weight"), md=md)
+        dz, dx = self._proj_ln_bwd(pfx + ".output.", sv["ln"], dY, sv["ctx"], ph, md)
         dctx = self._new(M, H)
         ops.gemm_nt(dx, self._wT(pfx + ".output.dense", P.w(pfx + ".output.dense.weight")), dctx, M_dev=md)
         dX = self._new(M, H)
@@ -596,23 +615,13 @@ class Engine:
         ops.gemm_nt(a, P.wb(lp + "intermediate.dense.weight"), h, bias=P.w(lp + "intermediate.dense.bias"),
                     epi=ops.EPI_GELU_DERIV if save else ops.EPI_GELU, C2=dact, M_dev=groups.rows_dev)
         salt = self._next_salt()
-        y, x, mean, rstd, y32 = self._proj_ln(h, P.wb(lp + "output.dense.weight"), P.w(lp + "output.dense.bias"), a, a32,
-                                              P.w(lp + "output.LayerNorm.weight"), P.w(lp + "output.LayerNorm.bias"), save=save,
-                                              eps=c.layer_norm_eps, ph=self._p_hidden(c), salt=salt, md=groups.rows_dev)
-        sv = dict(att=sv1, cross=sv2, a=a, h=h, dact=dact, z=x, y=y, mean=mean, rstd=rstd, salt=salt) if save else None
+        y, ln, y32 = self._proj_ln(lp + "output.", h, a, a32, save=save, eps=c.layer_norm_eps, ph=self._p_hidden(c), salt=salt, md=groups.rows_dev)
+        sv = dict(att=sv1, cross=sv2, a=a, h=h, dact=dact, ln=ln) if save else None
         return y, sv, y32
 
     def _layer_bwd(self, lp, c, sv, dY, groups, dkv_acc):
         P, H, I, M, md = self.P, c.hidden_size, c.intermediate_size, dY.shape[0], groups.rows_dev
-        ph = self._p_hidden(c)
-        dz = self._new(M, H)
-        dx = self._new(M, H) if ph > 0 else dz
-        from_y = sv["z"] is None
-        ops.ln_bwd(dY, sv["y"] if from_y else sv["z"], sv["mean"], sv["rstd"], P.w(lp + "output.LayerNorm.weight"), dz, dx=dx if ph > 0 else None,
-                   dgamma=P.g(lp + "output.LayerNorm.weight"), dbeta=P.g(lp + "output.LayerNorm.bias"), dropout_p=ph,
-                   seed=self.seed, salt=sv["salt"], dxsum=P.g(lp + "output.dense.bias"), rows_dev=md,
-                   beta_from_y=P.w(lp + "output.LayerNorm.bias") if from_y else None)
-        self._wgrad(dx, sv["h"], P.g(lp + "output.dense.weight"), md=md)
+        dz, dx = self._proj_ln_bwd(lp + "output.", sv["ln"], dY, sv["h"], self._p_hidden(c), md)
         dpre = self._new(M, I)
         ops.gemm_nt(dx, self._wT(lp + "output.dense", P.w(lp + "output.dense.weight")), dpre,
                     epi=ops.EPI_MUL, G=sv["dact"], colsum=P.g(lp + "intermediate.dense.bias"), M_dev=md)
@@ -649,90 +658,95 @@ class Engine:
         # asynchronous weight gradients beside the exchange (EngineOptions.dp_four_streams): the slice is final once the weight-gradient stream
         # AND the stream this layer's backward ran on are done with it -- the collective is issued from the weight-gradient stream behind an
         # event on the current one (ProcessGroupNCCL orders RCCL's stream behind the issuing stream); the backward itself does not wait
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        ws.wait_event(ev)
+        streams.after(ws, torch.cuda.current_stream())
         with torch.cuda.stream(ws):
             return self.layer_done_cb(prefix)
 
     # --------------------------------------------------------------------------------------------- embeddings
-    def embed_text(self, pfx, c, ids32, nseq, L, save):
+    def _embed(self, mode, pfx, c, nseq, L, save, salt, **src):
+        """One spmm_embed_ln_fwd launch: BertEmbeddings' position / type / LayerNorm parameters of `pfx` around the mode's sources (`src`).
+        -> (y, LnTape)"""
         P, H = self.P, c.hidden_size
         y = self._new(nseq * L, H)
         z = self._new(nseq * L, H) if save else None
-        mean = self._new(nseq * L, dtype=torch.float32) if save else None
-        rstd = self._new(nseq * L, dtype=torch.float32) if save else None
-        salt = self._next_salt()
-        ops.embed_ln_fwd(0, y, nseq=nseq, L=L, H=H, pos=P.w(pfx + "embeddings.position_embeddings.weight"),
+        mean, rstd = self._stats(nseq * L, save)
+        ops.embed_ln_fwd(mode, y, nseq=nseq, L=L, H=H, pos=P.w(pfx + "embeddings.position_embeddings.weight"),
                          type0=P.w(pfx + "embeddings.token_type_embeddings.weight"), gamma=P.w(pfx + "embeddings.LayerNorm.weight"),
-                         beta=P.w(pfx + "embeddings.LayerNorm.bias"), ids=ids32, word=P.w(pfx + "embeddings.word_embeddings.weight"),
-                         zout=z, mean=mean, rstd=rstd, eps=c.layer_norm_eps, dropout_p=self._p_hidden(c), seed=self.seed, salt=salt)
-        return y, dict(z=z, mean=mean, rstd=rstd, salt=salt)
+                         beta=P.w(pfx + "embeddings.LayerNorm.bias"), zout=z, mean=mean, rstd=rstd, eps=c.layer_norm_eps,
+                         dropout_p=self._p_hidden(c), seed=self.seed, salt=salt, **src)
+        return y, LnTape(z, None, mean, rstd, salt)
+
+    def embed_text(self, pfx, c, ids32, nseq, L, save):
+        return self._embed(0, pfx, c, nseq, L, save, self._next_salt(), ids=ids32, word=self.P.w(pfx + "embeddings.word_embeddings.weight"))
 
     def embed_pv(self, pfx, c, prop, mpm_mask, nseq, src_mod, save):
-        P, H, L = self.P, c.hidden_size, self.cfg.n_props + 1
-        y = self._new(nseq * L, H)
-        z = self._new(nseq * L, H) if save else None
-        mean = self._new(nseq * L, dtype=torch.float32) if save else None
-        rstd = self._new(nseq * L, dtype=torch.float32) if save else None
-        salt = self._next_salt()
-        ops.embed_ln_fwd(1, y, nseq=nseq, L=L, H=H, pos=P.w(pfx + "embeddings.position_embeddings.weight"),
-                         type0=P.w(pfx + "embeddings.token_type_embeddings.weight"), gamma=P.w(pfx + "embeddings.LayerNorm.weight"),
-                         beta=P.w(pfx + "embeddings.LayerNorm.bias"), pv_x=prop, pv_mask=mpm_mask, pv_w=P.w("property_embed.weight"),
-                         pv_b=P.w("property_embed.bias"), pv_cls=P.w("property_cls"), pv_masktok=P.w("property_mask"),
-                         src_mod=src_mod, zout=z, mean=mean, rstd=rstd, eps=c.layer_norm_eps, dropout_p=self._p_hidden(c),
-                         seed=self.seed, salt=salt)
-        return y, dict(z=z, mean=mean, rstd=rstd, salt=salt)
+        P = self.P
+        return self._embed(1, pfx, c, nseq, self.cfg.n_props + 1, save, self._next_salt(), pv_x=prop, pv_mask=mpm_mask,
+                           pv_w=P.w("property_embed.weight"), pv_b=P.w("property_embed.bias"), pv_cls=P.w("property_cls"),
+                           pv_masktok=P.w("property_mask"), src_mod=src_mod)
 
     def embed_generic(self, pfx, c, inputs_embeds_f32, nseq, L):
         """BertEmbeddings on caller-supplied inputs_embeds (xbert.py:199-219), inference only."""
-        P, H = self.P, c.hidden_size
-        y = self._new(nseq * L, H)
-        ops.embed_ln_fwd(2, y, nseq=nseq, L=L, H=H, pos=P.w(pfx + "embeddings.position_embeddings.weight"),
-                         type0=P.w(pfx + "embeddings.token_type_embeddings.weight"), gamma=P.w(pfx + "embeddings.LayerNorm.weight"),
-                         beta=P.w(pfx + "embeddings.LayerNorm.bias"), pv_x=inputs_embeds_f32, eps=c.layer_norm_eps,
-                         dropout_p=self._p_hidden(c), seed=self.seed, salt=self._next_salt())
-        return y
+        return self._embed(2, pfx, c, nseq, L, False, self._next_salt(), pv_x=inputs_embeds_f32)[0]
 
-    def _embed_ln_bwd(self, pfx, c, sv, dY):
+    def _embed_ln_bwd(self, pfx, c, tape, dY):
         P = self.P
         dz = self._new(*dY.shape)
-        ops.ln_bwd(dY, sv["z"], sv["mean"], sv["rstd"], P.w(pfx + "embeddings.LayerNorm.weight"), dz,
+        ops.ln_bwd(dY, tape.z, tape.mean, tape.rstd, P.w(pfx + "embeddings.LayerNorm.weight"), dz,
                    dgamma=P.g(pfx + "embeddings.LayerNorm.weight"), dbeta=P.g(pfx + "embeddings.LayerNorm.bias"),
-                   dropout_p=self._p_hidden(c), seed=self.seed, salt=sv["salt"], drop_on_dy=True)
+                   dropout_p=self._p_hidden(c), seed=self.seed, salt=tape.salt, drop_on_dy=True)
         return dz
 
-    # ------------------------------------------------------------------------------------------------ LM head
-    def lm_head_fwd(self, pfx, c, X, save):
-        """BertOnlyMLMHead xbert.py:662-706 -> fp32 logits [M, V]."""
-        P, H, V, M = self.P, c.hidden_size, c.vocab_size, X.shape[0]
-        t, pre = self._new(M, H), self._new(M, H)
-        ops.gemm_nt(X, P.wb(pfx + "cls.predictions.transform.dense.weight"), t, bias=P.w(pfx + "cls.predictions.transform.dense.bias"),
-                    epi=ops.EPI_GELU, C2=pre)
+    # ------------------------------------------------------------------------------------------------- heads
+    def _transform_fwd(self, dense, norm, X, save, *, eps, r32=False, pre=True):
+        """Transform head: Linear, erf-GELU, LayerNorm (BertPredictionHeadTransform xbert.py:662-676; property_mtr_head[0:3] SPMM_models.py:
+        39-42) as one GEMM with the GELU epilogue and one row kernel.  save: keep the LayerNorm's tape; pre: keep the pre-activation (the
+        GELU's backward reads it); r32 (fp32 residual stream): y is the fp32 twin the loss head reads.  -> (y, HeadTape)"""
+        P, M, H = self.P, X.shape[0], X.shape[1]
+        t = self._new(M, H)
+        pre = self._new(M, H) if pre else None
+        ops.gemm_nt(X, P.wb(dense + ".weight"), t, bias=P.w(dense + ".bias"), epi=ops.EPI_GELU, C2=pre)
         y = self._new(M, H)
-        mean = self._new(M, dtype=torch.float32) if save else None
-        rstd = self._new(M, dtype=torch.float32) if save else None
-        ops.ln_fwd(t, None, P.w(pfx + "cls.predictions.transform.LayerNorm.weight"), P.w(pfx + "cls.predictions.transform.LayerNorm.bias"),
-                   y, zout=t if save else None, mean=mean, rstd=rstd, eps=c.layer_norm_eps)
-        logits = self._new(M, V, dtype=torch.float32)
-        ops.gemm_nt(y, P.wb(pfx + "cls.predictions.decoder.weight"), logits, bias=P.w(pfx + "cls.predictions.bias"), epi=ops.EPI_F32)
-        return logits, dict(X=X, pre=pre, z=t, mean=mean, rstd=rstd, y=y)
+        mean, rstd = self._stats(M, save)
+        z = t if save else None                           # (the row kernel writes the sum over its own input)
+        kw = dict(zout=z, mean=mean, rstd=rstd, eps=eps)
+        if r32:
+            y32 = self._new(M, H, dtype=torch.float32)
+            ops.ln_fwd_r32(t, None, P.w(norm + ".weight"), P.w(norm + ".bias"), y, y32=y32, **kw)
+            y = y32
+        else:
+            ops.ln_fwd(t, None, P.w(norm + ".weight"), P.w(norm + ".bias"), y, **kw)
+        return y, HeadTape(dense, norm, X, pre, LnTape(z, y, mean, rstd))
 
-    def lm_head_bwd(self, pfx, c, sv, dlogits, out=None):
+    def _transform_bwd(self, tape, dy):
+        """Backward of `_transform_fwd` up to the pre-activation: -> dpre.  LayerNorm and dense-layer gradients are accumulated; the
+        data-gradient GEMM on dpre stays with the caller."""
+        P, ln = self.P, tape.ln
+        dz = self._new(*dy.shape)
+        ops.ln_bwd(dy, ln.z, ln.mean, ln.rstd, P.w(tape.norm + ".weight"), dz, dgamma=P.g(tape.norm + ".weight"), dbeta=P.g(tape.norm + ".bias"))
+        dpre = self._gelu_bwd(dz, tape.pre)
+        self._wgrad(dpre, tape.X, P.g(tape.dense + ".weight"), P.g(tape.dense + ".bias"))
+        return dpre
+
+    def lm_head_fwd(self, pfx, c, X, save):
+        """BertOnlyMLMHead xbert.py:662-706 -> (fp32 logits [M, V], HeadTape)."""
+        P = self.P
+        tf = pfx + "cls.predictions.transform."
+        y, tape = self._transform_fwd(tf + "dense", tf + "LayerNorm", X, save, eps=c.layer_norm_eps)
+        logits = self._new(X.shape[0], c.vocab_size, dtype=torch.float32)
+        ops.gemm_nt(y, P.wb(pfx + "cls.predictions.decoder.weight"), logits, bias=P.w(pfx + "cls.predictions.bias"), epi=ops.EPI_F32)
+        return logits, tape
+
+    def lm_head_bwd(self, pfx, c, tape, dlogits, out=None):
         """dlogits bf16 [M, Vpad] (zero padded) -> dX bf16 [M,H]; the decoder is tied to the word embeddings."""
         P, H, V, M = self.P, c.hidden_size, c.vocab_size, dlogits.shape[0]
         Vp = dlogits.shape[1]
         # wgrad of the tied decoder: dWord[V,H] += dlogits^T y ; dbias += colsum
         # (inline: the tied word-embedding gradient is also written by embed_bwd's atomics on the compute stream)
-        self._wgrad(dlogits[:, :V], sv["y"], P.g(pfx + "bert.embeddings.word_embeddings.weight"), P.g(pfx + "cls.predictions.bias"), inline=True)
+        self._wgrad(dlogits[:, :V], tape.ln.y, P.g(pfx + "bert.embeddings.word_embeddings.weight"), P.g(pfx + "cls.predictions.bias"), inline=True)
         dy = self._new(M, H)
         ops.gemm_nt(dlogits, P.wT_padded(pfx + "cls.decoderT", pfx + "bert.embeddings.word_embeddings.weight", Vp), dy)
-        dz = self._new(M, H)
-        ops.ln_bwd(dy, sv["z"], sv["mean"], sv["rstd"], P.w(pfx + "cls.predictions.transform.LayerNorm.weight"), dz,
-                   dgamma=P.g(pfx + "cls.predictions.transform.LayerNorm.weight"), dbeta=P.g(pfx + "cls.predictions.transform.LayerNorm.bias"))
-        # through the erf-GELU: dpre = dz * gelu'(pre)  (identity GEMM would be wasteful: reuse the GELU-grad epilogue of the dgrad)
-        dpre = self._gelu_bwd(dz, sv["pre"])
-        self._wgrad(dpre, sv["X"], P.g(pfx + "cls.predictions.transform.dense.weight"), P.g(pfx + "cls.predictions.transform.dense.bias"))
+        dpre = self._transform_bwd(tape, dy)
         dX = self._new(M, H) if out is None else out
         ops.gemm_nt(dpre, self._wT(pfx + "cls.transform", P.w(pfx + "cls.predictions.transform.dense.weight")), dX)
         return dX

@@ -128,14 +128,9 @@ class MtrHeadFacade:
     @torch.no_grad()
     def __call__(self, x):
         m = self._m
-        P, S = m._parameters, m.store
-        H = x.shape[-1]
-        x2 = x.to(m.device_).to(BF).reshape(-1, H).contiguous()
-        rows = x2.shape[0]
-        h = torch.empty(rows, H, dtype=BF, device=x2.device)
-        ops.gemm_nt(x2, S.wb("property_mtr_head.0.weight"), h, bias=S.w("property_mtr_head.0.bias"), epi=ops.EPI_GELU)
-        y = torch.empty_like(h)
-        ops.ln_fwd(h, None, S.w("property_mtr_head.2.weight"), S.w("property_mtr_head.2.bias"), y, eps=m.cfg.text.layer_norm_eps)
-        out = torch.empty(rows, 1, dtype=torch.float32, device=x2.device)
+        P = m._parameters
+        x2 = x.to(m.device_).to(BF).reshape(-1, x.shape[-1]).contiguous()
+        y, _ = m.engine._transform_fwd("property_mtr_head.0", "property_mtr_head.2", x2, False, eps=m.cfg.text.layer_norm_eps, pre=False)
+        out = torch.empty(x2.shape[0], 1, dtype=torch.float32, device=x2.device)
         ops.rows_linear(y, P["property_mtr_head.3.weight"].detach().contiguous(), P["property_mtr_head.3.bias"].detach(), out)
         return out.view(*x.shape[:-1], 1)

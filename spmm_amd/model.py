@@ -341,9 +341,11 @@ class SPMM(_Base):
         check = self._schedule_check_begin(grad_sync)
         eng.alpha.fill_(float(alpha))
         eng.gscale.fill_(1.0)
-        # (single-rank runs, and data-parallel ones with EngineOptions.dp_four_streams and a non-exclusive exchange; otherwise,
-        #  beside RCCL's stream, the weight-gradient stream shares a hardware slot with the caller's stream -- queue index
-        #  4 = 0 mod 4 -- and two streams that wait for each other there run the step at 74-76 ms instead of 57, profiles/r06_dp_one_rank.txt)
+        # Off-path maintenance on the weight-gradient stream (Engine.off_path): on single-rank runs, and on data-parallel ones under the default
+        # four-stream schedule (EngineOptions.dp_four_streams: caller, RCCL's, one side stream, weight-gradient) with a non-exclusive exchange.
+        # Not under round 5's five-stream data-parallel schedule: beside RCCL's stream the weight-gradient stream then shares a hardware slot
+        # with the caller's -- queue index 4 = 0 mod 4 -- and two streams that wait for each other there run the step at 74-76 ms instead of
+        # 57 (profiles/r06_dp_one_rank.txt).
         eng._off_path_ok = grad_sync is None or (self.options.dp_four_streams and getattr(grad_sync, "exclusive", True) is False)
         eng.off_path(lambda: ops.zero_(self.store.grad))        # nothing reads or writes a gradient before the backward
         dev = self.device_
@@ -379,7 +381,8 @@ class SPMM(_Base):
     # Data-parallel runs only (EngineOptions.schedule_check): the first SCHEDULE_CHECK_STEPS steps THAT CARRY A GRADIENT EXCHANGE try the
     # schedules this package cannot choose between without the node it runs on -- 4 steps on the side streams and 4 on one stream to warm up
     # (allocator pools grow while batches of new packed sizes arrive), then timed steps ROTATING between the candidates (four samples each,
-    # none always measured on the warmer clocks / pools): "three streams" (side streams, NT GEMMs one workgroup per tile under the exchange),
+    # none always measured on the warmer clocks / pools): "three streams" (the multi-stream schedule under its round-3 name, kept in the logged
+    # decision: with EngineOptions.dp_four_streams it runs on FOUR streams; NT GEMMs one workgroup per tile under the exchange),
     # "one stream", and -- with EngineOptions.nt_under_comm = "auto" -- "three streams, persistent NT" (faster by 1.3 ms per step when the
     # collectives' kernels are short, slower when ring kernels hold CUs for milliseconds: DESIGN.md 6).  The fastest of the two multi-stream
     # forms runs from then on (the persistent one only if its median wins by >= 1.5 %), the single stream only if ITS median wins by 13 % or

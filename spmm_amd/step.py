@@ -5,7 +5,7 @@ from typing import Callable, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import ops, streams
 from .engine import STREAM_TOKENS_MAX, BF, LOSS_ITA, LOSS_ITM, LOSS_MLM, LOSS_MPM, Batch, Engine, Group, KVSource, SelfKV, _ceil
 
 
@@ -137,8 +137,7 @@ class PretrainStep(Engine):
             ops.ema_update(P.flat_m, P.flat, P.shadow_m, cfg.momentum)
             P.refresh_frag(True)                 # (fragment-ordered images of the momentum cross-attention output projections)
             if side_m is not None:
-                ema_done = torch.cuda.Event()
-                ema_done.record(side_m)
+                ema_done = streams.mark(side_m)
             # momentum text branch (:104-105, :215-222), no tape
             x4, _ = self.embed_text("text_encoder_m.bert.", ct, ids2, 2 * B, Lt, False)
             x4_32 = f32(x4)
@@ -330,18 +329,8 @@ class PretrainStep(Engine):
 
         # ---- MPM (:241-256)
         hp12 = hp12_cls if cls_top else ypv[3 * B * Lp:]
-        mt, mpre = self._new(B * Lp, H), self._new(B * Lp, H)
-        ops.gemm_nt(hp12, P.wb("property_mtr_head.0.weight"), mt, bias=P.w("property_mtr_head.0.bias"), epi=ops.EPI_GELU, C2=mpre)
-        mln = self._new(B * Lp, H)
-        mmean, mrstd = self._new(B * Lp, dtype=torch.float32), self._new(B * Lp, dtype=torch.float32)
-        if r32:
-            mln_h = self._new(B * Lp, H, dtype=torch.float32)
-            ops.ln_fwd_r32(mt, None, P.w("property_mtr_head.2.weight"), P.w("property_mtr_head.2.bias"), mln, y32=mln_h, zout=mt, mean=mmean,
-                           rstd=mrstd, eps=ct.layer_norm_eps)
-        else:
-            mln_h = mln
-            ops.ln_fwd(mt, None, P.w("property_mtr_head.2.weight"), P.w("property_mtr_head.2.bias"), mln, zout=mt, mean=mmean, rstd=mrstd,
-                       eps=ct.layer_norm_eps)
+        # (the head keeps its LayerNorm tape on every forward: save=True)
+        mln_h, mpmsv = self._transform_fwd("property_mtr_head.0", "property_mtr_head.2", hp12, True, eps=ct.layer_norm_eps, r32=r32)
         pred = self._new(B, cfg.n_props, dtype=torch.float32) if aux is not None else None
         ops.mpm_head(mln_h, Lp, H, P.w("property_mtr_head.3.weight"), P.w("property_mtr_head.3.bias"), prop, mpm_mask, B=B,
                      ws=self.icount[4:8], losses=self.losses, slot=LOSS_MPM, pred=pred)
@@ -357,8 +346,7 @@ class PretrainStep(Engine):
             self.tape = dict(B=B, Lt=Lt, pk=pk, M=M, Mn=Mn, src_text=src_text, src_pv=src_pv, neg_rows=neg_rows, cls_text=cls_text, itm_text=itm_text,
                              prop=prop, mpm_mask=mpm_mask, ids32=ids32, ids2=ids2, esv1=esv1, g1=g1, tape1=tape1,
                              esv2=esv2, g2=g2, tape2=tape2, feats=feats, dfeat=dfeat, neg=neg, g6=g6, tape6=tape6, ypv=ypv_h,
-                             ytext=ytext, logits=logits, logits_m=logits_m, lmsv=lmsv, hp12=hp12, mpre=mpre, mt=mt, mln=mln_h,
-                             mmean=mmean, mrstd=mrstd, S6=S6 if cls_top else None)
+                             ytext=ytext, logits=logits, logits_m=logits_m, lmsv=lmsv, mpmsv=mpmsv, S6=S6 if cls_top else None)
         return self.losses[:4]
 
     # ----------------------------------------------------------------------------------------------- backward
@@ -388,14 +376,10 @@ class PretrainStep(Engine):
 
         # ---- MPM head
         dmln = self._new(B * Lp, H)
-        ops.mpm_head(T["mln"], Lp, H, P.w("property_mtr_head.3.weight"), P.w("property_mtr_head.3.bias"), T["prop"], T["mpm_mask"], B=B,
+        ops.mpm_head(T["mpmsv"].ln.y, Lp, H, P.w("property_mtr_head.3.weight"), P.w("property_mtr_head.3.bias"), T["prop"], T["mpm_mask"], B=B,
                      ws=self.icount[4:8], losses=scratch, slot=LOSS_MPM, dh=dmln, dw=P.g("property_mtr_head.3.weight"),
                      db=P.g("property_mtr_head.3.bias"), gscale=gs[1:2])
-        dmz = self._new(B * Lp, H)
-        ops.ln_bwd(dmln, T["mt"], T["mmean"], T["mrstd"], P.w("property_mtr_head.2.weight"), dmz,
-                   dgamma=P.g("property_mtr_head.2.weight"), dbeta=P.g("property_mtr_head.2.bias"))
-        dmpre = self._gelu_bwd(dmz, T["mpre"])
-        self._wgrad(dmpre, T["hp12"], P.g("property_mtr_head.0.weight"), P.g("property_mtr_head.0.bias"))
+        dmpre = self._transform_bwd(T["mpmsv"], dmln)
         ops.gemm_nt(dmpre, self._wT("property_mtr_head.0", P.w("property_mtr_head.0.weight")), dY_mpm)
 
         # ---- LM head

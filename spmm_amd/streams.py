@@ -52,6 +52,19 @@ def bind_in_order(device, names) -> None:
     torch.cuda.synchronize(idx)
 
 
+def mark(src: torch.cuda.Stream) -> torch.cuda.Event:
+    """An event recorded behind everything enqueued on `src` so far; whoever needs that work calls `wait_event` on it later."""
+    ev = torch.cuda.Event()
+    ev.record(src)
+    return ev
+
+
+def after(dst: torch.cuda.Stream, src: torch.cuda.Stream) -> None:
+    """The stream hand-off: `dst` waits for everything enqueued on `src` so far (one event; the host does not wait).  Every hand-off of
+    the step is this call or a `mark` / `wait_event` pair."""
+    dst.wait_event(mark(src))
+
+
 def handles(device=None) -> Dict[str, int]:
     return {n: s.cuda_stream for (i, n), s in _pool.items() if device is None or i == torch.device(device).index}
 

@@ -87,6 +87,24 @@ def test_step_schedule_dry_run(dry):
     assert log.count("spmm_attn_bwd") == 1 + 2 + 5 * 2
     assert log.count("spmm_fusion_plan") == 1 and log.count("spmm_pack_plan") == 1
     assert log.count("spmm_segment_sum_bf16") == 2              # one fold per shared key/value source (text, PV) per fusion layer
+    # The launch sequences of the sublayer helpers (Engine._proj_ln / _proj_ln_bwd, _transform_fwd / _transform_bwd, _embed), pinned for this
+    # step.  Chains: S1 PV student (1 layer), S2 text student (1 unimodal layer), S3 PV momentum (1), S4 text momentum (1 unimodal),
+    # S5 text momentum fusion (1 layer, no tape: its cross-attention block is the fused launch), S6 text student fusion (its top layer).
+    # LayerNorm forward: 2 sublayers (attention, FFN) x [S1 + S2 + S3 + S4 + S5] + 3 sublayers (attention, cross-attention, FFN) x S6
+    # + 3 transform heads (LM student, LM momentum, MPM)
+    assert log.count("spmm_ln_fwd") == 2 * 5 + 3 * 1 + 3 == 16
+    # LayerNorm backward, taped chains only: 2 x [S1 + S2] + 3 x S6 + 2 transform heads (LM, MPM) + 2 embeddings (text, PV)
+    assert log.count("spmm_ln_bwd") == 2 * 2 + 3 * 1 + 2 + 2 == 11
+    # weight gradients: 4 per unimodal layer (attention output, Q|K|V, FFN output, FFN intermediate) x [S1 + S2]; S6's top layer 10 = FFN 2
+    # + cross-attention 4 (output, K|V per shared source x 2, query) + self-attention 4 (output, Q|K|V, K|V of the two SelfKV sources);
+    # heads 5 = tied LM decoder + LM transform + MPM transform + the two ITA projections
+    assert log.count("spmm_gemm_tn") == 4 * 2 + 10 + 5 == 23
+    # bias gradients as a column-sum launch (those of the attention / FFN output projections come from spmm_ln_bwd's dxsum, the FFN
+    # intermediate's from its data-gradient GEMM's epilogue): Q|K|V x [S1 + S2]; S6's top layer 6 = self-attention Q|K|V + 2 SelfKV
+    # sources + cross-attention K|V x 2 sources + query; the 5 heads
+    assert log.count("spmm_colsum_bf16") == 1 * 2 + 6 + 5 == 13
+    # embeddings: text student (P2 | P10a in one launch), text momentum, PV student, PV momentum
+    assert log.count("spmm_embed_ln_fwd") == 2 + 2 == 4
     # autograd-boundary path
     dry._dry_log.clear()
     out = m(prop, ids, mask, alpha=0.1)
