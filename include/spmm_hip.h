@@ -200,6 +200,24 @@ int spmm_beam_step(const float* logits, long ldl, int N, int k, int V, int Lmax,
                    int* anc, int anc_ld, int* ids_out, int* parent_out, int* n_done, const int* mol, const int* rowmap,
                    spmm_stream_t stream);
 
+/* spmm_beam_step for the SAMPLED search (the stochastic branch of `generate`, d_pv2smiles_single.py:38-41): the arguments of spmm_beam_step,
+ * then noise [N*k, V] fp32 (row stride ldn >= V), the stream last as everywhere.  The k candidates of a beam are the k largest of
+ * key[j] = logits[j] + noise[j] (one fp32 add; ties to the lower index), in descending key order; their log-probabilities are those of the
+ * UNPERTURBED logits.  With the Gumbel noise of spmm_gumbel_noise that is k draws without replacement from the next-token distribution,
+ * in draw order (torch.multinomial(p, k, replacement=False)).  Finals, survivors, histories, ancestry, mol and rowmap as in spmm_beam_step. */
+int spmm_beam_step_sampled(const float* logits, long ldl, int N, int k, int V, int Lmax, int F, int t, const int* t_ptr, int t_off,
+                           int* tokens, float* cur_p, float* fin_p, int* fin_len, int* fin_tok, int* fin_n, unsigned char* done,
+                           int* anc, int anc_ld, int* ids_out, int* parent_out, int* n_done, const int* mol, const int* rowmap,
+                           const float* noise, long ldn, spmm_stream_t stream);
+
+/* Counter-based Gumbel noise for spmm_beam_step_sampled: out[ci*k + b, j] (row stride ldo) for compact molecule ci < N, beam b < k, token
+ * j < V is g = -log(-log(u)), u = ((h >> 8) + 0.5) * 2^-24 (never 0 or 1), h = rng_pair(seed_mix(*seed_ptr, salt), idx) (csrc/common.h) with the
+ * 64-bit counter idx = (((mol_base + n) * Lmax + t) * k + b) * V + j, n = mol ? mol[ci] : ci (spmm_beam_step's convention), t = *t_ptr + t_off
+ * when t_ptr is given.  A draw depends on (seed, salt, GLOBAL molecule index, position, beam, token) only -- not on the batch the molecule is
+ * decoded in, the chunking of a run or compactions.  k <= 8, V <= 512, Lmax <= 256, 0 <= t < Lmax, N*k*V < 2^31. */
+int spmm_gumbel_noise(const uint64_t* seed_ptr, uint64_t salt, int N, int k, int V, int Lmax, int t, const int* t_ptr, int t_off,
+                      const int* mol, long mol_base, float* out, long ldo, spmm_stream_t stream);
+
 /* mode 0: BertEmbeddings.forward xbert.py:193-220 from token ids.  mode 1: the PV path -- property_embed Linear(1,H),
  * bernoulli mask blend with property_mask, property_cls prepend (SPMM_models.py:82-88) fused with BertEmbeddings
  * (inputs_embeds branch).  Sequence s reads PV source row s % src_mod.  mode 2: generic inputs_embeds branch of

@@ -1,0 +1,187 @@
+"""PV -> SMILES generation driver -- the counterpart of the reference's d_pv2smiles_single.py (flags, one property vector, n samples,
+stochastic k-beam search with k = 2, any subset of the 53 properties left unspecified):
+
+  python pv2smiles.py --checkpoint ./Pretrain/checkpoint_SPMM.ckpt --vocab_filename ./vocab_bpe_300.txt --input p2s_input.csv \
+                      --property_names property_name.txt --normalize normalize.pkl --n_generate 1000 --k 2 --seed 7
+  python pv2smiles.py --synthetic --tiny --n_generate 8 --seed 1                          (no data files: seeded weights, PV and vocabulary)
+
+What differs from the reference, on purpose: the seed is a flag (the reference draws one at random) and the same seed gives the same
+molecules whatever `--chunk` is; all samples of a chunk are decoded together against a K/V cache (spmm_amd.decode.generate_with_property);
+the conditions come from `--input` / `--property_names` instead of files next to the script; the CSV is read with the csv module; validity
+and the normalised RMSE of the controlled properties are reported only where RDKit is installed."""
+import argparse
+import csv
+import os
+import pickle
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+N_PROPS = 53
+
+
+def str2bool(s) -> bool:
+    return str(s).lower() in ("1", "true", "yes", "y")
+
+
+# ------------------------------------------------------------------------------------------------------------------- conditions
+def read_condition(input_csv: str, property_names: str):
+    """d_pv2smiles_single.py:186-195: `property,input_value` rows -> (prop_input [53], prop_mask [53]); a property that the file does not
+    name is masked (1) and its input is 0.  property_names: one name per line, the line number is the property's index."""
+    with open(property_names) as f:
+        index = {line.strip(): i for i, line in enumerate(f) if line.strip()}
+    prop_input, prop_mask = torch.zeros(len(index)), torch.ones(len(index))
+    with open(input_csv, newline="") as f:
+        for row in csv.DictReader(f):
+            name = row["property"].strip()
+            if name not in index:
+                raise SystemExit(f"{input_csv}: unknown property {name!r} (not in {property_names})")
+            prop_input[index[name]] = float(row["input_value"])
+            prop_mask[index[name]] = 0
+    return prop_input, prop_mask
+
+
+def read_normalize(path: str):
+    """(mean [53], std [53]) from the reference's normalize.pkl (a pickled pair) or an .npz with `mean` and `std`."""
+    if path.endswith(".npz"):
+        z = np.load(path)
+        mean, std = z["mean"], z["std"]
+    else:
+        with open(path, "rb") as f:
+            mean, std = pickle.load(f)
+    return torch.as_tensor(np.asarray(mean), dtype=torch.float32), torch.as_tensor(np.asarray(std), dtype=torch.float32)
+
+
+def synthetic_vocab(size: int):
+    """Specials at the reference's ids, then `size - 4` made-up continuation pieces (decoding needs names, nothing else)."""
+    atoms = ["C", "c", "N", "n", "O", "o", "S", "s", "F", "Cl", "Br", "(", ")", "=", "#", "1", "2", "3", "4", "[nH]"]
+    pieces = ["##" + a for a in atoms] + ["##" + a + b for a in atoms for b in atoms]
+    return ["[PAD]", "[UNK]", "[CLS]", "[SEP]"] + pieces[: size - 4]
+
+
+# ------------------------------------------------------------------------------------------------------------------- metrics
+def report(samples, smiles, prop_input, prop_mask, norm, names):
+    n = len(samples)
+    none = sum(1 for s in samples if not s)
+    done = [s for s in smiles if s]
+    print(f"samples: {n}")
+    print(f"without a final hypothesis: {none}")
+    print(f"uniqueness (strings): {len(set(done)) / max(len(done), 1):.4f}")
+    try:
+        from rdkit import Chem
+        from rdkit.Chem import Descriptors
+    except ImportError:
+        print("validity / normalised RMSE: not computed (RDKit is not installed)")
+        return
+    mols = [(s, Chem.MolFromSmiles(s)) for s in done]
+    valid = [(s, m) for s, m in mols if m is not None]
+    print(f"validity: {len(valid) / max(n, 1):.4f}")
+    canon = {Chem.MolToSmiles(m, isomericSmiles=False) for _, m in valid}
+    print(f"uniqueness (canonical, among valid): {len(canon) / max(len(valid), 1):.4f}")
+    if norm is None or names is None or not valid:
+        return
+    mean, std = norm
+    ctrl = [i for i in range(len(names)) if prop_mask[i] == 0 and hasattr(Descriptors, names[i])]
+    if not ctrl:
+        return
+    err = []
+    for _, m in valid:
+        got = torch.tensor([float(getattr(Descriptors, names[i])(m)) for i in ctrl])
+        err.append(((got - mean[ctrl]) / std[ctrl] - (prop_input[ctrl] - mean[ctrl]) / std[ctrl]) ** 2)
+    rmse = torch.sqrt(torch.stack(err).mean(0))
+    print(f"mean of controlled properties' normalized RMSE: {rmse.mean().item():.4f}")
+
+
+# ------------------------------------------------------------------------------------------------------------------- main
+def main(args):
+    device = torch.device(args.device)
+    torch.manual_seed(args.seed)
+    from spmm_amd import decode
+    from spmm_amd.model import SPMM
+    from spmm_amd.tokenizer import SmilesWordPiece
+
+    cfg_dir = os.path.join(ROOT, "configs")
+    tiny = "_tiny" if args.tiny else ""
+    config = {"embed_dim": 64 if args.tiny else 256, "queue_size": 16 if args.tiny else 36864,
+              "bert_config_text": os.path.join(cfg_dir, f"config_bert{tiny}.json"),
+              "bert_config_property": os.path.join(cfg_dir, f"config_bert_property{tiny}.json")}
+    if os.path.exists(args.vocab_filename):
+        tokenizer = SmilesWordPiece(args.vocab_filename)
+    elif args.synthetic:
+        tokenizer = None                                   # (made below, once the model's vocabulary size is known)
+    else:
+        raise SystemExit(f"--vocab_filename {args.vocab_filename} not found (needed to decode the generated ids)")
+    print("Creating model")
+    model = SPMM(config=config, tokenizer=tokenizer, no_train=True, device=device)
+    if tokenizer is None:
+        tokenizer = model.tokenizer = SmilesWordPiece(synthetic_vocab(model.cfg.text.vocab_size))
+    names = None
+    if args.property_names:
+        with open(args.property_names) as f:
+            names = [line.strip() for line in f if line.strip()]
+    norm = read_normalize(args.normalize) if args.normalize else None
+    if args.synthetic:
+        # seeded weights (torch.manual_seed above) with [SEP] made a likely token, so that the searches of an untrained model end;
+        # a seeded PV with every third property left unspecified
+        sd = model.state_dict()
+        g = torch.Generator().manual_seed(args.seed)
+        bias = torch.randn(sd["text_encoder.cls.predictions.bias"].shape, generator=g) * 1.5
+        bias[decode.SEP_ID] = bias.max() - 0.5
+        model.load_state_dict({"text_encoder.cls.predictions.bias": bias, "text_encoder.cls.predictions.decoder.bias": bias}, strict=False)
+        prop_input = torch.randn(N_PROPS, generator=g)
+        prop_mask = (torch.arange(N_PROPS) % 3 == 0).float()
+    else:
+        if args.checkpoint:
+            print("LOADING PRETRAINED MODEL..")
+            res = model.load_checkpoint(args.checkpoint, weights_only=True)
+            print(f"load checkpoint from {args.checkpoint} (missing {len(res.missing_keys)}, unexpected {len(res.unexpected_keys)})")
+        if args.input:
+            if not args.property_names:
+                raise SystemExit("--input needs --property_names (one property name per line)")
+            prop_input, prop_mask = read_condition(args.input, args.property_names)
+        else:                                              # nothing specified: unconditional generation (every property masked)
+            prop_input, prop_mask = torch.zeros(N_PROPS), torch.ones(N_PROPS)
+    model.eval()
+    pv = prop_input if norm is None or args.synthetic else (prop_input - norm[0]) / norm[1]
+    print(f"PV-to-SMILES generation in {'stochastic' if args.stochastic else 'deterministic'} manner with k={args.k}, seed {args.seed}...")
+    samples = decode.generate_with_property(model, pv.to(device), args.n_generate, prop_mask.to(device), k=args.k, stochastic=args.stochastic,
+                                            seed=args.seed, max_steps=args.max_steps, chunk=args.chunk or None)
+    smiles = [tokenizer.decode(s) for s in samples]
+    with open(args.output, "w") as f:
+        for s in smiles:
+            f.write(s + "\n")
+    print("=" * 50)
+    report(samples, smiles, prop_input, prop_mask, norm, names)
+    print(f"Generated molecules are saved in '{args.output}'")
+    print("=" * 50)
+    return smiles
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser()
+    # the reference's flags (d_pv2smiles_single.py:227-233)
+    p.add_argument("--checkpoint", default="./Pretrain/checkpoint_SPMM.ckpt")
+    p.add_argument("--vocab_filename", default="./vocab_bpe_300.txt")
+    p.add_argument("--device", default="cuda")
+    p.add_argument("--n_generate", default=1000, type=int)
+    p.add_argument("--k", default=2, type=int)
+    p.add_argument("--stochastic", default=True, type=str2bool)
+    # additions
+    p.add_argument("--seed", default=0, type=int, help="seed of the draws (and of --synthetic's weights and PV): same seed, same molecules")
+    p.add_argument("--input", default="", help="CSV with the columns property,input_value: the properties to control (the others are masked)")
+    p.add_argument("--property_names", default="", help="one property name per line; line i names property i")
+    p.add_argument("--normalize", default="", help="mean / std of the properties: the reference's normalize.pkl, or an .npz with mean and std")
+    p.add_argument("--output", default="generated_molecules.txt")
+    p.add_argument("--max_steps", default=100, type=int, help="positions decoded at most")
+    p.add_argument("--chunk", default=0, type=int, help="samples decoded together (0: all)")
+    p.add_argument("--synthetic", action="store_true", help="no data files: seeded weights, property vector and vocabulary")
+    p.add_argument("--tiny", action="store_true", help="2-layer / 128-d encoders (configs/config_bert_tiny.json)")
+    return p.parse_args(argv)
+
+
+if __name__ == "__main__":
+    main(parse_args())

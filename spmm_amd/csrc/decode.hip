@@ -428,6 +428,7 @@ struct BeamP {
   int* anc; int anc_ld; int* ids_out; int* parent_out; int* n_done;
   const int* mol;              // optional: state index (tokens, scores, finals, flags) of compact molecule i -- the live subset after a compaction
   const int* rowmap;           // optional: K/V cache row of compact beam row i*k + b (the "own row" written into the ancestry table)
+  const float* noise; long ldn;   // SAMPLED instantiation: [N*k, >= V] fp32 added to the logits for the candidate selection only
 };
 constexpr int BEAM_KMAX = 8, BEAM_SEP = 3;
 
@@ -440,7 +441,11 @@ __device__ __forceinline__ void wave_argmax(float& v, int& i) {        // ties -
   }
 }
 
-template <int VJ>
+// SAMPLED: the k candidates of a beam are the k largest of key[j] = logit[j] + noise[j] (one fp32 add, ties to the lower index), taken in
+// descending key order; with Gumbel noise (spmm_gumbel_noise) that is k draws without replacement from the next-token distribution, in
+// draw order (the stochastic branch of `generate`, d_pv2smiles_single.py:38-41).  The recorded log-probability is that of the UNPERTURBED
+// logit; everything after the candidates is the same code.
+template <int VJ, bool SAMPLED>
 __global__ __launch_bounds__(256) void beam_step_kernel(BeamP p) {
   const int lane = threadIdx.x & 63;
   const int ci = blockIdx.x * 4 + (threadIdx.x >> 6);                   // compact molecule index: rows ci*k .. of logits / ids / anc
@@ -467,17 +472,39 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamP p) {
     for (int j = 0; j < VJ; ++j) s += lane + 64 * j < p.V ? expf(v[j] - m) : 0.f;
     s = wave_sum(s);
     const float cp = p.cur_p[n * k + b];
-    for (int r = 0; r < k; ++r) {
-      float bv = NEG;
-      int bi = 0x7fffffff;
+    if constexpr (SAMPLED) {
+      const float* nrow = p.noise + (long)(ci * k + b) * p.ldn;
+      float key[VJ];                                                    // lanes beyond V keep -inf
 #pragma unroll
-      for (int j = 0; j < VJ; ++j)
-        if (v[j] > bv) { bv = v[j]; bi = lane + 64 * j; }
-      wave_argmax(bv, bi);
+      for (int j = 0; j < VJ; ++j) key[j] = lane + 64 * j < p.V ? __fadd_rn(v[j], nrow[lane + 64 * j]) : NEG;      // (never contracted into an fma)
+      for (int r = 0; r < k; ++r) {
+        float bv = NEG;
+        int bi = 0x7fffffff;
 #pragma unroll
-      for (int j = 0; j < VJ; ++j)
-        if (lane + 64 * j == bi) v[j] = NEG;
-      if (lane == b * k + r) { my_lp = cp + logf(expf(bv - m) / s); my_tok = bi; }      // log(softmax(x)[i]) as the reference forms it
+        for (int j = 0; j < VJ; ++j)
+          if (key[j] > bv) { bv = key[j]; bi = lane + 64 * j; }
+        wave_argmax(bv, bi);
+        bi = min(bi, p.V - 1);                                          // (a row of NaN / -inf noise selects nothing: still a token of the vocabulary)
+        float lv = 0.f;                                                 // the winner's own logit, from the lane that holds it
+#pragma unroll
+        for (int j = 0; j < VJ; ++j)
+          if (lane + 64 * j == bi) { lv = v[j]; key[j] = NEG; }
+        lv = __shfl(lv, bi & 63, 64);
+        if (lane == b * k + r) { my_lp = cp + logf(expf(lv - m) / s); my_tok = bi; }
+      }
+    } else {
+      for (int r = 0; r < k; ++r) {
+        float bv = NEG;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < VJ; ++j)
+          if (v[j] > bv) { bv = v[j]; bi = lane + 64 * j; }
+        wave_argmax(bv, bi);
+#pragma unroll
+        for (int j = 0; j < VJ; ++j)
+          if (lane + 64 * j == bi) v[j] = NEG;
+        if (lane == b * k + r) { my_lp = cp + logf(expf(bv - m) / s); my_tok = bi; }      // log(softmax(x)[i]) as the reference forms it
+      }
     }
   }
   // ---- finals, in row-major candidate order
@@ -579,20 +606,80 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamP p) {
   }
 }
 
+// ---- Gumbel noise for the sampled search, from a counter: element (molecule, position, beam, token) hashes its own 64-bit index, so a
+// draw does not depend on which other molecules share the launch, on the chunking of a run or on compactions.
+struct GumbelP {
+  const uint64_t* seed_ptr; uint64_t salt; int k, V, Lmax; int t; const int* t_ptr; int t_off; const int* mol; long mol_base;
+  float* out; long ldo; unsigned total;
+};
+
+__global__ __launch_bounds__(256) void gumbel_noise_kernel(GumbelP p) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;                   // element of the [N*k, V] block
+  if (i >= p.total) return;
+  const unsigned row = i / (unsigned)p.V, j = i - row * (unsigned)p.V;
+  const unsigned ci = row / (unsigned)p.k, b = row - ci * (unsigned)p.k;
+  const long n = p.mol ? p.mol[ci] : (long)ci;                          // state index, as in beam_step_kernel
+  const long t = p.t_ptr ? *p.t_ptr + p.t_off : p.t;
+  const uint64_t idx = ((((uint64_t)(p.mol_base + n) * (uint64_t)p.Lmax + (uint64_t)t) * (uint64_t)p.k + b) * (uint64_t)p.V) + j;
+  const uint32_t x = rng_pair(seed_mix(p.seed_ptr, p.salt), idx) >> 8;  // 24 bits: u = (x + 0.5) * 2^-24 lies strictly inside (0, 1)
+  // a = -log(u).  x + 0.5 is exact in fp32 only below 2^23; above it (u >= 1/2) 1 - u = (2^24 - 1 - x + 0.5) * 2^-24 is, and a = -log1p(-(1 - u)):
+  // formed as logf(u) there, the top of the range would round to u = 1 and the noise to +inf.
+  float a;
+  if (x < (1u << 23)) a = -logf(((float)x + 0.5f) * (1.0f / 16777216.0f));
+  else a = -log1pf(-(((float)(0xffffffu - x) + 0.5f) * (1.0f / 16777216.0f)));
+  p.out[(long)row * p.ldo + j] = -logf(a);
+}
+
+int beam_step_launch(BeamP p, hipStream_t stream, const char* who) {
+  SPMM_CHECK_SHAPE(p.N > 0 && p.k >= 1 && p.k <= BEAM_KMAX && p.V >= p.k && p.V <= 512 && p.Lmax >= 3 && p.Lmax <= 256 && p.F >= p.k && p.ldl >= p.V,
+                   "%s: N=%d k=%d V=%d Lmax=%d F=%d (k <= 8, k <= V <= 512, Lmax <= 256, F >= k)", who, p.N, p.k, p.V, p.Lmax, p.F);
+  SPMM_CHECK_SHAPE(p.anc == nullptr || p.anc_ld >= p.Lmax, "%s: anc_ld=%d < Lmax=%d", who, p.anc_ld, p.Lmax);
+  SPMM_CHECK_SHAPE(p.t_ptr != nullptr || (p.t >= 1 && p.t < p.Lmax), "%s: t=%d outside [1, Lmax)", who, p.t);
+  const dim3 grid((unsigned)((p.N + 3) / 4));
+  if (p.noise) {
+    SPMM_CHECK_SHAPE(p.ldn >= p.V, "%s: noise row stride %ld < V=%d", who, p.ldn, p.V);
+    if (p.V <= 320) hipLaunchKernelGGL((beam_step_kernel<5, true>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((beam_step_kernel<8, true>), grid, dim3(256), 0, stream, p);
+  } else {
+    if (p.V <= 320) hipLaunchKernelGGL((beam_step_kernel<5, false>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((beam_step_kernel<8, false>), grid, dim3(256), 0, stream, p);
+  }
+  SPMM_LAUNCH_CHECK(who);
+  return SPMM_OK;
+}
+
 }  // namespace
 
 extern "C" int spmm_beam_step(const float* logits, long ldl, int N, int k, int V, int Lmax, int F, int t, const int* t_ptr, int t_off,
                               int* tokens, float* cur_p, float* fin_p, int* fin_len, int* fin_tok, int* fin_n, unsigned char* done,
                               int* anc, int anc_ld, int* ids_out, int* parent_out, int* n_done, const int* mol, const int* rowmap,
                               hipStream_t stream) {
-  SPMM_CHECK_SHAPE(N > 0 && k >= 1 && k <= BEAM_KMAX && V >= k && V <= 512 && Lmax >= 3 && Lmax <= 256 && F >= k && ldl >= V,
-                   "spmm_beam_step: N=%d k=%d V=%d Lmax=%d F=%d (k <= 8, k <= V <= 512, Lmax <= 256, F >= k)", N, k, V, Lmax, F);
-  SPMM_CHECK_SHAPE(anc == nullptr || anc_ld >= Lmax, "spmm_beam_step: anc_ld=%d < Lmax=%d", anc_ld, Lmax);
-  SPMM_CHECK_SHAPE(t_ptr != nullptr || (t >= 1 && t < Lmax), "spmm_beam_step: t=%d outside [1, Lmax)", t);
-  BeamP p = {logits, ldl, N, k, V, Lmax, F, t, t_ptr, t_off, tokens, cur_p, fin_p, fin_len, fin_tok, fin_n, done, anc, anc_ld, ids_out, parent_out, n_done, mol, rowmap};
-  const dim3 grid((unsigned)((N + 3) / 4));
-  if (V <= 320) hipLaunchKernelGGL(beam_step_kernel<5>, grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL(beam_step_kernel<8>, grid, dim3(256), 0, stream, p);
-  SPMM_LAUNCH_CHECK("spmm_beam_step");
+  BeamP p = {logits, ldl, N, k, V, Lmax, F, t, t_ptr, t_off, tokens, cur_p, fin_p, fin_len, fin_tok, fin_n, done, anc, anc_ld, ids_out, parent_out, n_done, mol, rowmap,
+             nullptr, 0};
+  return beam_step_launch(p, stream, "spmm_beam_step");
+}
+
+extern "C" int spmm_beam_step_sampled(const float* logits, long ldl, int N, int k, int V, int Lmax, int F, int t, const int* t_ptr, int t_off,
+                                      int* tokens, float* cur_p, float* fin_p, int* fin_len, int* fin_tok, int* fin_n, unsigned char* done,
+                                      int* anc, int anc_ld, int* ids_out, int* parent_out, int* n_done, const int* mol, const int* rowmap,
+                                      const float* noise, long ldn, hipStream_t stream) {
+  SPMM_CHECK_SHAPE(noise != nullptr, "spmm_beam_step_sampled: noise is required (spmm_beam_step is the deterministic search)");
+  BeamP p = {logits, ldl, N, k, V, Lmax, F, t, t_ptr, t_off, tokens, cur_p, fin_p, fin_len, fin_tok, fin_n, done, anc, anc_ld, ids_out, parent_out, n_done, mol, rowmap,
+             noise, ldn};
+  return beam_step_launch(p, stream, "spmm_beam_step_sampled");
+}
+
+extern "C" int spmm_gumbel_noise(const uint64_t* seed_ptr, uint64_t salt, int N, int k, int V, int Lmax, int t, const int* t_ptr, int t_off,
+                                 const int* mol, long mol_base, float* out, long ldo, hipStream_t stream) {
+  SPMM_CHECK_SHAPE(seed_ptr != nullptr && out != nullptr, "spmm_gumbel_noise: seed and output are required");
+  SPMM_CHECK_SHAPE(N > 0 && k >= 1 && k <= BEAM_KMAX && V >= 1 && V <= 512 && Lmax >= 1 && Lmax <= 256 && ldo >= V && mol_base >= 0,
+                   "spmm_gumbel_noise: N=%d k=%d V=%d Lmax=%d ldo=%ld mol_base=%ld (k <= 8, V <= 512, ldo >= V, Lmax <= 256, mol_base >= 0)", N, k, V, Lmax, ldo,
+                   mol_base);
+  SPMM_CHECK_SHAPE(t_ptr != nullptr || (t >= 0 && t < Lmax), "spmm_gumbel_noise: t=%d outside [0, Lmax)", t);
+  const long total = (long)N * k * V;
+  SPMM_CHECK_SHAPE(total < (1L << 31), "spmm_gumbel_noise: N*k*V=%ld does not fit 31 bits", total);
+  GumbelP p = {seed_ptr, salt, k, V, Lmax, t, t_ptr, t_off, mol, mol_base, out, ldo, (unsigned)total};
+  hipLaunchKernelGGL(gumbel_noise_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p);
+  SPMM_LAUNCH_CHECK("spmm_gumbel_noise");
   return SPMM_OK;
 }

@@ -5,8 +5,10 @@ restated in oracle/decode_oracle.py -- test infrastructure, the yard-stick of te
 from __future__ import annotations
 
 import functools
+import random
 from typing import List, Tuple
 
+import numpy as np
 import torch
 
 CLS_ID, SEP_ID = 2, 3           # vocab_bpe_300.txt:3-4
@@ -16,6 +18,8 @@ GRAPH_BELOW_ROWS = 200          # beam rows below which one hipGraph replay per 
 last_run: dict = {}             # what the last eager beam_search_batched did: molecules, compactions, final_batch, positions
 COMPACT_BELOW = 0.75            # the batch is re-gathered once at most this share of its molecules is still live
 FUSED_BEAM_STEP = True          # beam bookkeeping of a position as one HIP launch (spmm_beam_step); False: the tensor-op form (BeamBook.update)
+GUMBEL_SALT = 0x50563253        # call-site salt of the sampled search's noise ("PV2S"; dropout and negative sampling use small integers)
+last_generate: dict = {}        # what the last generate_with_property did: samples, no_final, chunks
 
 
 def _pick(p: torch.Tensor, k: int, stochastic: bool, generator=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -27,6 +31,54 @@ def _pick(p: torch.Tensor, k: int, stochastic: bool, generator=None) -> Tuple[to
         return torch.log(flat.gather(1, ids)).reshape(*p.shape[:-1], k), ids.reshape(*p.shape[:-1], k)
     top = torch.topk(p, k=k, dim=-1)
     return torch.log(top.values), top.indices
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Seeded sampling: Gumbel noise from a counter.  Adding independent Gumbel(0, 1) noise to the logits and taking the k largest, in
+# descending order, IS k draws without replacement from softmax(logits), in draw order (Gumbel-top-k) -- what torch.multinomial(p, k,
+# replacement=False) does in the reference.  Every element hashes its own index (global molecule, position, beam, token), so a molecule's
+# draws do not depend on the batch it is decoded in.  Device form: csrc/decode.hip::gumbel_noise_kernel; this is the same arithmetic on
+# the host (integers identical, the transform in float64).
+# ------------------------------------------------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(z: int) -> int:
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def gumbel_bits_host(seed: int, salt: int, mol_ids, t: int, k: int, V: int, Lmax: int) -> np.ndarray:
+    """The 24-bit integers x = rng_pair(seed_mix(seed, salt), idx) >> 8 of csrc/common.h for idx = ((mol * Lmax + t) * k + b) * V + j:
+    int64 [len(mol_ids), k, V].  mol_ids are GLOBAL molecule indices (mol_base + n)."""
+    key = _splitmix64((_splitmix64(int(seed) & _M64) + int(salt)) & _M64)
+    mol = np.asarray(mol_ids, dtype=np.uint64).reshape(-1, 1, 1)
+    b = np.arange(k, dtype=np.uint64).reshape(1, k, 1)
+    j = np.arange(V, dtype=np.uint64).reshape(1, 1, V)
+    with np.errstate(over="ignore"):
+        idx = ((mol * np.uint64(Lmax) + np.uint64(t)) * np.uint64(k) + b) * np.uint64(V) + j
+        lo, hi = (idx & np.uint64(0xFFFFFFFF)).astype(np.uint32), (idx >> np.uint64(32)).astype(np.uint32)
+        x = (lo ^ np.uint32(key & 0xFFFFFFFF)) + (hi ^ np.uint32(key >> 32)) * np.uint32(0x9E3779B1)
+        x ^= x >> np.uint32(16); x *= np.uint32(0x21F0AAAD)
+        x ^= x >> np.uint32(15); x *= np.uint32(0x735A2D97)
+        x ^= x >> np.uint32(15)
+    return (x >> np.uint32(8)).astype(np.int64)
+
+
+def gumbel_noise_host(seed: int, salt: int, mol_ids, t: int, k: int, V: int, Lmax: int) -> torch.Tensor:
+    """Gumbel noise of ops.gumbel_noise on the host: float64 [len(mol_ids) * k, V], g = -log(-log(u)), u = (x + 0.5) * 2^-24 in (0, 1)."""
+    u = (gumbel_bits_host(seed, salt, mol_ids, t, k, V, Lmax).astype(np.float64) + 0.5) * 2.0 ** -24
+    return torch.from_numpy(-np.log(-np.log(u))).reshape(-1, V)
+
+
+def _pick_seeded(logits: torch.Tensor, noise: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The sampled branch of `_pick` with explicit noise, on LOGITS [..., V]: ids = the k largest of logits + noise in descending order,
+    log-probs = log_softmax(logits) at those ids (unperturbed) -> (log-probs, ids) [..., k].  The tensor-op twin of the SAMPLED
+    instantiation of csrc/decode.hip::beam_step_kernel: both form the keys with the same single fp32 add."""
+    ids = torch.topk(logits + noise.to(logits.dtype).reshape(logits.shape), k=k, dim=-1).indices
+    return torch.log_softmax(logits, dim=-1).gather(-1, ids), ids
 
 
 @torch.no_grad()
@@ -141,12 +193,13 @@ class BeamBook:
         self.mol = cur[keep].contiguous()
 
     def step_fused(self, logits: torch.Tensor, anc: torch.Tensor | None = None, t_ptr: torch.Tensor | None = None, t_off: int = 0,
-                   ids_out: torch.Tensor | None = None, rowmap: torch.Tensor | None = None) -> torch.Tensor:
+                   ids_out: torch.Tensor | None = None, rowmap: torch.Tensor | None = None, noise: torch.Tensor | None = None) -> torch.Tensor:
         """`update` (and the decoder's ancestry reorder) as one HIP launch on the next-token logits [N*k, V]: softmax, the k best successors
         per beam, finals, survivors, token histories, `anc` -- all in place.  Returns the tokens to feed next (int32 [N*k]).  With t_ptr
-        (device int32 [1]) the number of tokens held comes from device memory (*t_ptr + t_off) and self.t is left to the caller."""
+        (device int32 [1]) the number of tokens held comes from device memory (*t_ptr + t_off) and self.t is left to the caller.  With noise
+        (fp32 [N*k, V]) the k successors of a beam are the k largest of logits + noise: the sampled search."""
         from . import ops
-        ids = ops.beam_step(logits, self, t=self.t, t_ptr=t_ptr, t_off=t_off, anc=anc, ids_out=ids_out, rowmap=rowmap)
+        ids = ops.beam_step(logits, self, t=self.t, t_ptr=t_ptr, t_off=t_off, anc=anc, ids_out=ids_out, rowmap=rowmap, noise=noise)
         if t_ptr is None:
             self.t += 1
         return ids
@@ -198,7 +251,9 @@ class CachedDecoder:
     K/V projected once per molecule and shared by its k beams (cache slots sketched at
     xbert.py:291-295,480,1344-1348)."""
 
-    def __init__(self, model, prop_embeds: torch.Tensor, k: int, Lmax: int):
+    def __init__(self, model, prop_embeds: torch.Tensor, k: int, Lmax: int, repeat: int = 1, xkv: dict | None = None):
+        """repeat: decode `repeat` molecules per row of prop_embeds (generation of many samples from one PV: the cross-attention keys /
+        values are projected once per row and copied).  xkv: the projections of an earlier decoder on the same prop_embeds (`xkv_once`)."""
         from . import ops
         from .engine import BF
         self.ops, self.BF = ops, BF
@@ -207,6 +262,7 @@ class CachedDecoder:
         self.pfx = "text_encoder."
         c, dev = self.c, model.device_
         N, Lkv, H = prop_embeds.shape
+        N *= repeat
         assert Lmax <= 256 and H == c.hidden_size and c.hidden_size // c.num_attention_heads == 64
         self.N, self.R, self.Lmax, self.Lp, self.H = N, N * k, Lmax, Lkv, H
         nl = c.num_hidden_layers
@@ -216,13 +272,16 @@ class CachedDecoder:
         self.anc = torch.arange(self.R, dtype=torch.int32, device=dev)[:, None].repeat(1, Lmax).contiguous()
         self.rows = torch.arange(self.R, dtype=torch.int32, device=dev)
         self.rowmap = None                               # after compact(): cache row of every beam row still decoded (None: the row itself)
-        kv_src = prop_embeds.to(dev).to(BF).reshape(N * Lkv, H).contiguous()
-        self.xkv = {}
-        for l in range(c.fusion_layer, nl):
-            pf = f"{self.pfx}bert.encoder.layer.{l}.crossattention.self."
-            KV = torch.empty(N * Lkv, 2 * H, dtype=BF, device=dev)
-            ops.gemm_nt(kv_src, self.P.fused(pf, ("key", "value"), "weight"), KV, bias=self.P.fused(pf, ("key", "value"), "bias", what="w"))
-            self.xkv[l] = KV
+        if xkv is None:
+            kv_src = prop_embeds.to(dev).to(BF).reshape(-1, H).contiguous()
+            xkv = {}
+            for l in range(c.fusion_layer, nl):
+                pf = f"{self.pfx}bert.encoder.layer.{l}.crossattention.self."
+                KV = torch.empty(kv_src.shape[0], 2 * H, dtype=BF, device=dev)
+                ops.gemm_nt(kv_src, self.P.fused(pf, ("key", "value"), "weight"), KV, bias=self.P.fused(pf, ("key", "value"), "bias", what="w"))
+                xkv[l] = KV
+        self.xkv_once = xkv                              # per row of prop_embeds
+        self.xkv = {l: (KV.view(-1, Lkv, 2 * H).repeat_interleave(repeat, dim=0).reshape(-1, 2 * H) if repeat > 1 else KV) for l, KV in xkv.items()}
 
     def _new(self, *shape, dtype=None):
         return torch.empty(*shape, dtype=dtype or self.BF, device=self.anc.device)
@@ -296,37 +355,67 @@ class CachedDecoder:
 @torch.no_grad()
 def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int = 100, cached: bool | None = None,
                         sync_every: int = 4, prop_mask: torch.Tensor | None = None, stochastic: bool = False,
-                        generator=None, graph: bool | None = None, compact: bool = True) -> List[List[Tuple[float, List[int]]]]:
+                        generator=None, graph: bool | None = None, compact: bool = True, seed: int | None = None,
+                        mol_base: int = 0) -> List[List[Tuple[float, List[int]]]]:
     """The reference's beam search for N molecules at once (props [N,53]); result[n] is what the one-molecule search
     (oracle/decode_oracle.py::beam_search) returns for props[n].
     cached=True (default on the HIP model) decodes one token per step against the K/V cache; cached=False re-runs the prefix
     through the module API (any model exposing it, e.g. the CPU oracle).  prop_mask: properties to leave unspecified
     (encode_properties).  stochastic=True draws the k candidates of every beam from the next-token distribution instead of
-    taking the k most probable (d_pv2smiles_single.py:37-40); `generator` seeds those draws.  graph=True (cached, deterministic)
-    captures one decode position -- ~230 launches -- as a hipGraph and replays it: the per-position host cost drops from ~2.3 ms
-    of launch overhead to one graph launch, which is what small batches are bound by.  graph=None (default): replay when the batch
-    is launch-bound -- fewer than GRAPH_BELOW_ROWS beam rows -- and the search is deterministic.  compact=True (eager fused path): finished
+    taking the k most probable (d_pv2smiles_single.py:37-40).  Without `seed` the draws are torch.multinomial's, from `generator`, on the
+    tensor-op bookkeeping.  With `seed` every position -- position 0 from [CLS] included (t = 0, b = 0) -- draws by Gumbel-top-k from
+    counter noise keyed by (seed, mol_base + n, position, beam, token) (ops.gumbel_noise / gumbel_noise_host): molecule mol_base + n gets
+    the same draws whatever batch it is decoded in, the search runs on the one-launch beam step under the same conditions as the
+    deterministic one, and finished molecules are dropped (`compact`) as they are there.
+    graph=True (cached, deterministic) captures one decode position -- ~230 launches -- as a hipGraph and replays it: the per-position
+    host cost drops from ~2.3 ms of launch overhead to one graph launch, which is what small batches are bound by.  graph=None (default):
+    replay when the batch is launch-bound -- fewer than GRAPH_BELOW_ROWS beam rows -- and the search is deterministic.  A sampled search
+    (seeded or not) stays eager whatever `graph` says.  compact=True (eager fused path): finished
     molecules are dropped from the batch as the search goes (same results; the reference decodes one molecule at a time and simply stops)."""
-    last_run.clear()
     if cached is None:
         cached = hasattr(model, "engine")
+    prop_embeds = encode_properties(model, props, prop_mask)
+    if cached:
+        model.engine.train_mode = False
+    dec = (CachedDecoder if cached else RecomputeDecoder)(model, prop_embeds, k, max_steps + 3)
+    return _search(model, dec, prop_embeds.shape[0], k, max_steps, cached, sync_every, stochastic, generator, graph, compact, seed, mol_base)
+
+
+def _search(model, dec, N: int, k: int, max_steps: int, cached: bool, sync_every: int, stochastic: bool, generator, graph, compact: bool,
+            seed: int | None, mol_base: int):
+    """beam_search_batched behind the decoder's construction (generate_with_property builds its decoders from one encoded PV)."""
+    last_run.clear()
     if graph is None:
         # Replay is OPT-IN (graph=True) since round 5: every call re-captures its ~130 kernels (a graph is tied to this call's buffers), capture
         # is process-global on the capture stream's device -- another thread touching the GPU meanwhile aborts it -- and a replayed graph
         # cannot drop finished molecules (`compact`).  It gains 7 % at 100 beam rows and nothing from 500 on (GRAPH_BELOW_ROWS).
         graph = False
-    prop_embeds = encode_properties(model, props, prop_mask)
-    N, dev = prop_embeds.shape[0], prop_embeds.device
-    if cached:
-        model.engine.train_mode = False
-    dec = (CachedDecoder if cached else RecomputeDecoder)(model, prop_embeds, k, max_steps + 3)
+    dev = dec.anc.device if cached else dec.kv.device
+    Lmax = max_steps + 3
+    seeded = bool(stochastic and seed is not None)
     # one launch per position for the beam bookkeeping (csrc/decode.hip::beam_step_kernel: k <= 8 beams, vocabulary <= 512, histories <= 256
     # tokens -- the tensor-op bookkeeping serves everything else)
-    fused = bool(cached and not stochastic and k <= 8 and FUSED_BEAM_STEP and model.cfg.text.vocab_size <= 512 and max_steps + 3 <= 256)
+    fused = bool(cached and (seeded or not stochastic) and k <= 8 and FUSED_BEAM_STEP and model.cfg.text.vocab_size <= 512 and Lmax <= 256)
     book = BeamBook(N, k, max_steps, dev, fused=fused)
     ids = torch.full((N * k,), CLS_ID, dtype=torch.long, device=dev)
     logits = dec.step(ids, 0).view(N, k, -1)[:, 0]                       # all k rows hold the same [CLS] prefix
-    values, indices = _pick(torch.softmax(logits.float(), dim=-1), k, stochastic, generator)
+    if seeded:
+        V = logits.shape[-1]
+        dev_noise = bool(cached and k <= 8 and V <= 512 and Lmax <= 256)          # (what spmm_gumbel_noise accepts; else the host form)
+        if dev_noise:
+            from . import ops
+            seed_dev = torch.tensor([(int(seed) & _M64) - ((int(seed) & (1 << 63)) << 1)], dtype=torch.int64, device=dev)
+            nbuf = torch.empty(N * k, V, dtype=torch.float32, device=dev)
+
+        def noise_at(t: int, n_cur: int) -> torch.Tensor:
+            """fp32 [n_cur*k, V] for the molecules now in the batch, after `t` generated tokens"""
+            if dev_noise:
+                return ops.gumbel_noise(seed_dev, n_cur, k, V, Lmax, salt=GUMBEL_SALT, t=t, mol=book.mol, mol_base=mol_base, out=nbuf[:n_cur * k])
+            return gumbel_noise_host(seed, GUMBEL_SALT, range(mol_base, mol_base + N), t, k, V, Lmax).to(torch.float32).to(dev)
+
+        values, indices = _pick_seeded(logits.float(), noise_at(0, N).view(N, k, V)[:, 0], k)
+    else:
+        values, indices = _pick(torch.softmax(logits.float(), dim=-1), k, stochastic, generator)
     book.first(values, indices)
     ids = indices.reshape(N * k)
     if graph and cached and not stochastic:
@@ -336,9 +425,12 @@ def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int =
     for s in range(max_steps):
         logits = dec.step(ids, s + 1)
         if fused:
-            ids = book.step_fused(logits, dec.anc, rowmap=dec.rowmap)
+            ids = book.step_fused(logits, dec.anc, rowmap=dec.rowmap, noise=noise_at(s + 1, n_cur) if seeded else None)
         else:
-            values, indices = _pick(torch.softmax(logits.view(N, k, -1).float(), dim=-1), k, stochastic, generator)
+            if seeded:
+                values, indices = _pick_seeded(logits.view(N, k, -1).float(), noise_at(s + 1, N), k)
+            else:
+                values, indices = _pick(torch.softmax(logits.view(N, k, -1).float(), dim=-1), k, stochastic, generator)
             parent, tok = book.update(values, indices)
             dec.reorder(parent, s + 2)
             ids = tok.reshape(N * k)
@@ -365,6 +457,43 @@ def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int =
                     last_run["final_batch"] = n_cur
         last_run["positions"] = s + 1
     return book.results()
+
+
+@torch.no_grad()
+def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: torch.Tensor | None = None, k: int = 2, stochastic: bool = True,
+                           seed: int = 0, max_steps: int = 100, chunk: int | None = None) -> List[List[int]]:
+    """`generate_with_property` of d_pv2smiles_single.py:54-111: n_sample molecules from ONE (normalised) property vector pv [53], with the
+    properties of prop_mask ([53], 1 = unspecified) replaced by the mask token.  Returns one token-id list per sample ([CLS] ... [SEP]; empty
+    when the search of that sample finished nothing -- counted in last_generate["no_final"]).
+    The PV is encoded once, on one row; the cross-attention keys / values are projected once per fusion layer and copied for the samples of
+    a chunk (`chunk` samples are decoded together; None: all of them).  Sample i is molecule i of the seeded search (beam_search_batched(seed=...,
+    mol_base=...)), so the samples do not depend on the chunking.  As in the reference (:102-110) a stochastic run returns one of each sample's
+    up-to-k finals, picked by random.Random(seed) on the host in sample order; a deterministic run returns the best final."""
+    cached = hasattr(model, "engine")
+    prop_embeds = encode_properties(model, pv.reshape(1, -1), None if prop_mask is None else prop_mask.reshape(1, -1))
+    if cached:
+        model.engine.train_mode = False
+    chunk = n_sample if not chunk else min(int(chunk), n_sample)
+    rng = random.Random(seed)
+    out: List[List[int]] = []
+    xkv, none = None, 0
+    for base in range(0, n_sample, chunk):
+        n = min(chunk, n_sample - base)
+        if cached:
+            dec = CachedDecoder(model, prop_embeds, k, max_steps + 3, repeat=n, xkv=xkv)
+            xkv = dec.xkv_once
+        else:
+            dec = RecomputeDecoder(model, prop_embeds.expand(n, -1, -1), k, max_steps + 3)
+        res = _search(model, dec, n, k, max_steps, cached, 4, stochastic, None, False, True, seed if stochastic else None, base)
+        for finals in res:
+            if not finals:
+                none += 1
+                out.append([])
+            else:
+                out.append(finals[rng.randrange(len(finals)) if stochastic else 0][1])
+    last_generate.clear()
+    last_generate.update(samples=n_sample, no_final=none, chunks=(n_sample + chunk - 1) // chunk)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -474,9 +474,10 @@ def decode_attn(q, K, V, out, *, nH, Lkv, seq_stride, tok_stride, head_stride=64
     return out
 
 
-def beam_step(logits, book, *, t=0, t_ptr=None, t_off=0, anc=None, ids_out=None, parent_out=None, rowmap=None):
+def beam_step(logits, book, *, t=0, t_ptr=None, t_off=0, anc=None, ids_out=None, parent_out=None, rowmap=None, noise=None):
     """One position of the batched k-beam search on a decode.BeamBook with int32 state (csrc/decode.hip::beam_step_kernel): updates
-    the book (and the ancestry table `anc` of the K/V cache) in place and returns the tokens to feed next, int32 [N*k]."""
+    the book (and the ancestry table `anc` of the K/V cache) in place and returns the tokens to feed next, int32 [N*k].  noise (fp32
+    [N*k, V], e.g. from gumbel_noise): the sampled search -- candidates by logits + noise, log-probabilities of the logits themselves."""
     _, k, L = book.tokens.shape
     mol = getattr(book, "mol", None)                      # int32 [N]: the live molecules of a compacted batch (None: all of them)
     N = book.tokens.shape[0] if mol is None else mol.numel()
@@ -487,10 +488,29 @@ def beam_step(logits, book, *, t=0, t_ptr=None, t_off=0, anc=None, ids_out=None,
     assert anc is None or (anc.dtype == torch.int32 and anc.shape[0] == N * k and anc.stride(1) == 1)
     if ids_out is None:
         ids_out = torch.empty(N * k, dtype=torch.int32, device=logits.device)
-    _call("spmm_beam_step", _p(logits), logits.stride(0), N, k, logits.shape[1], L, book.F, int(t), _p(t_ptr), int(t_off), _p(book.tokens),
-          _p(book.cur_p), _p(book.fin_p), _p(book.fin_len), _p(book.fin_tok), _p(book.fin_n), _p(book.done), _p(anc),
-          0 if anc is None else anc.stride(0), _p(ids_out), _p(parent_out), _p(book.n_done), _p(mol), _p(rowmap), _st())
+    args = (_p(logits), logits.stride(0), N, k, logits.shape[1], L, book.F, int(t), _p(t_ptr), int(t_off), _p(book.tokens),
+            _p(book.cur_p), _p(book.fin_p), _p(book.fin_len), _p(book.fin_tok), _p(book.fin_n), _p(book.done), _p(anc),
+            0 if anc is None else anc.stride(0), _p(ids_out), _p(parent_out), _p(book.n_done), _p(mol), _p(rowmap))
+    if noise is None:
+        _call("spmm_beam_step", *args, _st())
+    else:
+        assert noise.dtype == torch.float32 and noise.dim() == 2 and noise.stride(1) == 1 and noise.device == logits.device
+        assert noise.shape[0] == N * k and noise.shape[1] >= logits.shape[1], (noise.shape, logits.shape)
+        _call("spmm_beam_step_sampled", *args, _p(noise), noise.stride(0), _st())
     return ids_out
+
+
+def gumbel_noise(seed, N, k, V, Lmax, *, salt=0, t=0, t_ptr=None, t_off=0, mol=None, mol_base=0, out=None):
+    """Counter-based Gumbel noise for the sampled beam step (csrc/decode.hip::gumbel_noise_kernel): fp32 [N*k, V]; element (ci, b, j) is a
+    function of (seed, salt, mol_base + (mol[ci] if mol is given else ci), t, b, j) alone.  seed: int64 [1] on the device (the bit pattern
+    of the 64-bit seed); t_ptr (int32 [1], device): the position is *t_ptr + t_off instead of t."""
+    assert seed.dtype == torch.int64 and seed.numel() == 1
+    assert mol is None or (mol.dtype == torch.int32 and mol.numel() == N and mol.is_contiguous())
+    if out is None:
+        out = torch.empty(N * k, V, dtype=torch.float32, device=seed.device)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == N * k and out.shape[1] >= V and out.stride(1) == 1
+    _call("spmm_gumbel_noise", _p(seed), int(salt), N, k, V, Lmax, int(t), _p(t_ptr), int(t_off), _p(mol), int(mol_base), _p(out), out.stride(0), _st())
+    return out
 
 
 def segment_sum_bf16(src, start, lst, out):
