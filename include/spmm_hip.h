@@ -305,6 +305,20 @@ int spmm_itm_head(const void* xa, long stride_a, const void* xb, long stride_b, 
 int spmm_task_head(const void* A, long lda, int B, int W, const float* W2, const float* b2, int C, int kind, const void* target,
                    const float* gscale, float* logits, float* loss, void* dA, long ldda, float* dW2, float* db2, int do_bwd,
                    spmm_stream_t stream);
+/* One launch that closes step i of the SMILES -> PV regression loop (d_smiles2pv.py:14-52) and opens step i + 1, for `rows` molecules.
+ * y [rows, H] bf16 (row stride ldy): the transform part of property_mtr_head (Linear, GELU, LayerNorm; SPMM_models.py:39-41) on the
+ * last-position rows.  Per row r:  p = b3[0] + sum_h y[r,h] w3[h] in fp32 (property_mtr_head.3, :42) -> pred[r*ldp + i];  then, unless
+ * i == n_props - 1 (no next step: the cache is not touched), the embedded prefix row of position j = i + 1,
+ *   LayerNorm(p pe_w + pe_b + pos[j] + type0) gamma + beta   (property_embed :36; BertEmbeddings, inputs_embeds branch xbert.py:209-218:
+ *   the zero token type's row IS added there -- type0 null leaves it out), as bf16 -> xcache[(r*Lc + j)*H ..], Lc = n_props + 1.
+ * xcache [rows, Lc, H] is the append-only cache of embedded prefix rows (row 0: the embedded property_cls, written by the caller);
+ * w3, pe_w, pe_b, type0, gamma, beta: fp32 [H]; b3: fp32 [1]; pos: the PV encoder's position table [>= Lc, H]; all device memory.
+ * One wave per row.  H a multiple of 64 up to 1024, 0 <= i < n_props, ldy >= H (a multiple of 4), ldp >= n_props.
+ * Alignment: the fp32 vectors (w3, pe_w, pe_b, pos, type0, gamma, beta) are read 16 bytes at a time and y / xcache 8 bytes at a time, so
+ * their base pointers must be 16-byte (y, xcache: 8-byte) aligned; violations are reported as a bad argument. */
+int spmm_s2p_append(const void* y, long ldy, const float* w3, const float* b3, const float* pe_w, const float* pe_b, const float* pos,
+                    const float* type0, const float* gamma, const float* beta, float eps, float* pred, long ldp, void* xcache,
+                    long rows, int H, int n_props, int i, spmm_stream_t stream);
 /* property_mtr_head final Linear(H,1) + masked MSE * 5 SPMM_models.py:251-256.  n_keep_ws: 4 ints, 8-byte aligned (as n_nonpad_ws). */
 int spmm_mpm_head(const void* h, int Lp, int H, const float* w, const float* bias, const float* target, const float* mask,
                   int B, int* n_keep_ws, const float* gscale, float* losses, int loss_slot, float* pred_out, void* dh,

@@ -11,6 +11,10 @@
 // 64 columns of W2: dW2 over every row in a fixed order; workgroup 0 also forms db2 and the mean loss, again in a fixed order).
 // So two launches on the same inputs agree bit for bit.  The shapes are tiny (B <= 1024, C <= 64, W <= 4096): launch count, not
 // bandwidth or FLOPs, is what this costs.
+//
+// Also here: spmm_s2p_append, the launch that closes one step of the SMILES -> PV regression loop (d_smiles2pv.py:14-52) and opens the
+// next: the last Linear(H, 1) of property_mtr_head on the last-position rows, then property_embed + BertEmbeddings (inputs_embeds
+// branch) of the predicted value, written as the next row of the append-only cache of embedded prefix rows.
 #include "common.h"
 #include "../../include/spmm_hip.h"
 
@@ -172,5 +176,106 @@ extern "C" int spmm_task_head(const void* A, long lda, int B, int W, const float
                        gscale, logits, loss, dW2, db2, do_bwd);
     SPMM_LAUNCH_CHECK("spmm_task_head");
   }
+  return SPMM_OK;
+}
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------------------ spmm_s2p_append
+// One wave per row r (four rows per workgroup): the row of H <= 1024 values stays in registers, S2P_MAXC chunks of four per lane
+// (8-byte bf16 loads / stores, 16-byte fp32 loads).
+//   p = b3 + sum_h y[r,h] w3[h]                          fp32, lane-local chunks then the wave butterfly      -> pred[r*ldp + i]
+//   e[h] = p pe_w[h] + pe_b[h] + pos_j[h] (+ type0[h])   property_embed (SPMM_models.py:36), xbert.py:209-217
+//   xrow[r*Lc*H + h] = LN(e)[h] gamma[h] + beta[h]        two-pass variance as in ln_apply (csrc/rowops.hip); xrow = xcache + j*H, null: no next step
+constexpr int S2P_MAXC = 4;
+__global__ __launch_bounds__(256) void s2p_append_kernel(const bf16* __restrict__ y, long ldy, const float* __restrict__ w3,
+                                                         const float* __restrict__ b3, const float* __restrict__ pe_w,
+                                                         const float* __restrict__ pe_b, const float* __restrict__ pos_j,
+                                                         const float* __restrict__ type0, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, float eps, float* __restrict__ pred, long ldp,
+                                                         int i, bf16* __restrict__ xrow, long seq_stride, long rows, int H) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const bf16* yr = y + r * ldy;
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < S2P_MAXC; ++k) {
+    const int c = (lane + 64 * k) * 4;
+    if (c < H) {
+      const bf16x4 a = *(const bf16x4*)(yr + c);
+      const f32x4 w = *(const f32x4*)(w3 + c);
+      s += ((float)a[0] * w[0] + (float)a[1] * w[1]) + ((float)a[2] * w[2] + (float)a[3] * w[3]);
+    }
+  }
+  const float p = wave_sum(s) + b3[0];                // (the butterfly leaves the same sum in every lane)
+  if (lane == 0) pred[r * ldp + i] = p;
+  if (!xrow) return;
+  float e[S2P_MAXC][4];
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < S2P_MAXC; ++k) {
+    const int c = (lane + 64 * k) * 4;
+    if (c < H) {
+      const f32x4 w = *(const f32x4*)(pe_w + c), b = *(const f32x4*)(pe_b + c), ps = *(const f32x4*)(pos_j + c);
+      f32x4 t = {0.f, 0.f, 0.f, 0.f};
+      if (type0) t = *(const f32x4*)(type0 + c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        e[k][j] = (p * w[j] + b[j]) + (ps[j] + t[j]);
+        sum += e[k][j];
+      }
+    } else {
+      e[k][0] = e[k][1] = e[k][2] = e[k][3] = 0.f;
+    }
+  }
+  const float mean = wave_sum(sum) / H;
+  float ss = 0.f;
+#pragma unroll
+  for (int k = 0; k < S2P_MAXC; ++k) {
+    const int c = (lane + 64 * k) * 4;
+    if (c < H) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { const float d = e[k][j] - mean; ss += d * d; }
+    }
+  }
+  const float var = wave_sum(ss) / H;
+  float rstd = rsqrtf(var + eps);
+  if (!(var + eps > 0.f)) rstd = 0.f;                 // an all-equal row with an eps that underflows: zeros, not NaN (as ln_apply)
+  bf16* out = xrow + r * seq_stride;
+#pragma unroll
+  for (int k = 0; k < S2P_MAXC; ++k) {
+    const int c = (lane + 64 * k) * 4;
+    if (c < H) {
+      const f32x4 gm = *(const f32x4*)(gamma + c), bt = *(const f32x4*)(beta + c);
+      *(bf16x4*)(out + c) = to_bf16x4((e[k][0] - mean) * rstd * gm[0] + bt[0], (e[k][1] - mean) * rstd * gm[1] + bt[1],
+                                      (e[k][2] - mean) * rstd * gm[2] + bt[2], (e[k][3] - mean) * rstd * gm[3] + bt[3]);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int spmm_s2p_append(const void* y, long ldy, const float* w3, const float* b3, const float* pe_w, const float* pe_b,
+                               const float* pos, const float* type0, const float* gamma, const float* beta, float eps, float* pred,
+                               long ldp, void* xcache, long rows, int H, int n_props, int i, hipStream_t stream) {
+  SPMM_CHECK_SHAPE(rows >= 1 && rows <= (1l << 24), "spmm_s2p_append: rows=%ld (1 <= rows <= 2^24)", rows);
+  SPMM_CHECK_SHAPE(H >= 64 && H % 64 == 0 && H <= 256 * S2P_MAXC, "spmm_s2p_append: H=%d (a multiple of 64 up to %d)", H, 256 * S2P_MAXC);
+  SPMM_CHECK_SHAPE(n_props >= 1 && i >= 0 && i < n_props, "spmm_s2p_append: step i=%d of n_props=%d (0 <= i < n_props)", i, n_props);
+  SPMM_CHECK_SHAPE(ldy >= H && ldy % 4 == 0, "spmm_s2p_append: ldy=%ld (at least H=%d, a multiple of 4)", ldy, H);
+  SPMM_CHECK_SHAPE(ldp >= n_props, "spmm_s2p_append: ldp=%ld (at least n_props=%d)", ldp, n_props);
+  SPMM_CHECK_SHAPE(y && w3 && b3 && pred, "spmm_s2p_append: y, w3, b3 and pred are required");
+  const auto mis = [](const void* q, uintptr_t n) { return ((uintptr_t)q & (n - 1)) != 0; };
+  SPMM_CHECK_SHAPE(!mis(y, 8) && !mis(xcache, 8) && !mis(w3, 16) && !mis(pe_w, 16) && !mis(pe_b, 16) && !mis(pos, 16) && !mis(type0, 16) &&
+                       !mis(gamma, 16) && !mis(beta, 16),
+                   "spmm_s2p_append: misaligned pointer (y, xcache: 8 bytes; w3, pe_w, pe_b, pos, type0, gamma, beta: 16 bytes)");
+  const bool next = i + 1 < n_props;                  // the last step opens no further one: the cache is not written
+  SPMM_CHECK_SHAPE(!next || (pe_w && pe_b && pos && gamma && beta && xcache),
+                   "spmm_s2p_append: step %d of %d appends a cache row: pe_w, pe_b, pos, gamma, beta and xcache are required", i, n_props);
+  const long j = i + 1, Lc = (long)n_props + 1;
+  hipLaunchKernelGGL(s2p_append_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, (const bf16*)y, ldy, w3, b3, pe_w, pe_b,
+                     next ? pos + j * H : nullptr, type0, gamma, beta, eps, pred, ldp, i, next ? (bf16*)xcache + j * H : nullptr, Lc * H,
+                     rows, H);
+  SPMM_LAUNCH_CHECK("spmm_s2p_append");
   return SPMM_OK;
 }

@@ -525,6 +525,108 @@ def smiles_to_pv(model, text_ids: torch.Tensor, text_mask: torch.Tensor, n_props
     return torch.stack(out, dim=-1)
 
 
+class S2PDecoder:
+    """`smiles_to_pv` on the engine.  What does not change between the steps is computed once: the text is encoded once on packed rows
+    (padding rows dropped, as the fine-tuning step packs them), the cross-attention keys | values of every fusion layer are projected
+    once from it, and the embedded prefix rows live in an append-only cache `xcache` [B, n_props + 1, H] -- the embedded row of prefix
+    position j depends on the value at j and on j alone.  The PV encoder is bidirectional, so every hidden state of the prefix changes
+    at every step: nothing else can be cached.  A step is launches only -- the row count B * n is host data -- and its last fusion
+    layer runs on the B last-position rows, the only ones read afterwards, with self-attention keys / values projected from all B * n
+    rows (engine.SelfKV).  `pred` [B, n_props] fp32 fills one column per step (ops.s2p_append)."""
+    TP = "text_encoder.bert."
+
+    @torch.no_grad()
+    def __init__(self, model, text_ids: torch.Tensor, text_mask: torch.Tensor, n_props: int = 53):
+        from . import ops
+        from .engine import BF, Batch, Group, KVSource
+        eng = model.engine
+        eng.train_mode = False
+        self.ops, self.eng, self.P, self.ct, self.cp = ops, eng, eng.P, model.cfg.text, model.cfg.prop
+        ct, cp, P, dev = self.ct, self.cp, eng.P, model.device_
+        H, f, nl = ct.hidden_size, ct.fusion_layer, ct.num_hidden_layers
+        B, Lt = text_ids.shape
+        Lc = n_props + 1
+        if Lc > cp.max_position_embeddings:
+            raise ValueError(f"{n_props} properties need {Lc} positions; the PV encoder has {cp.max_position_embeddings}")
+        if Lt > ct.max_position_embeddings:
+            raise ValueError(f"sequence length {Lt} exceeds the {ct.max_position_embeddings} position embeddings")
+        self.B, self.n_props, self.Lc, self.H = B, n_props, Lc, H
+        # ---- the text, once: embeddings, packed rows, unimodal layers
+        n_tokens = None
+        if text_mask.device.type == "cpu":               # a host mask of non-empty prefixes sizes the packed batch without a device read
+            lens = text_mask.sum(1)
+            if bool((lens > 0).all()) and bool(((torch.arange(Lt)[None, :] < lens[:, None]) == (text_mask != 0)).all()):
+                n_tokens = int(lens.sum())
+        ids32 = text_ids.to(dev).to(torch.int32).contiguous()
+        mask32 = text_mask.to(dev).to(torch.int32).contiguous()
+        x, _ = eng.embed_text(self.TP, ct, ids32, B, Lt, False)
+        pk = eng._pack_plan(mask32, B, Lt, n_tokens) if (eng.pack_text and Lt <= ops.ATTN_MAXL) else None
+        if pk:
+            x = ops.gather_rows2(eng._new(pk["M"], H), x, pk["rows"])
+            g = Batch([Group(0, B, Lt, None, B, q_row0=pk["row0"], q_len=pk["len"], nrows=pk["M"])])
+        else:
+            g = Batch([Group(0, B, Lt, mask32, B)])
+        text, _, _ = eng.stack_fwd(self.TP, ct, range(0, f), False, x, g, False)
+        # ---- cross-attention keys | values of every fusion layer, once
+        proj = {}
+        for l in range(f, nl):
+            pf = f"{self.TP}encoder.layer.{l}.crossattention"
+            proj[pf] = ops.gemm_nt(text, P.fused(pf + ".self.", ("key", "value"), "weight"), eng._new(text.shape[0], 2 * H),
+                                   bias=P.fused(pf + ".self.", ("key", "value"), "bias", what="w"))
+        self.src = KVSource(text, B, Lt, row0=pk["row0"], length=pk["len"], proj=proj) if pk else KVSource(text, B, Lt, proj=proj)
+        self.kv_mask = None if pk else mask32            # (packed: the source's lengths are the key mask)
+        self.ar = torch.arange(B, dtype=torch.int32, device=dev)
+        # ---- index arrays of all steps, once: step i gathers rows (b, 0..i) of the cache and keeps row (b, i) for the last layer
+        b_ = np.arange(B, dtype=np.int64)[:, None]
+        gather = [(b_ * Lc + np.arange(i + 1, dtype=np.int64)[None, :]).reshape(-1) for i in range(n_props)]
+        self.off = np.concatenate([[0], np.cumsum([a.size for a in gather])])
+        self.idx = torch.from_numpy(np.concatenate(gather)).to(dev)
+        steps = np.arange(1, n_props + 1, dtype=np.int64)[:, None]
+        self.last = torch.from_numpy(np.ascontiguousarray(b_.T * steps + steps - 1)).to(dev)                 # int64 [n_props, B]
+        self.row0 = torch.from_numpy(np.ascontiguousarray((b_.T * steps).astype(np.int32))).to(dev)         # int32 [n_props, B]
+        self.lens = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(steps, (n_props, B)).astype(np.int32))).to(dev)
+        # ---- the cache: row 0 of every molecule is the embedded property_cls (BertEmbeddings, inputs_embeds branch)
+        self.xcache = torch.empty(B, Lc, H, dtype=BF, device=dev)
+        cls = P.w("property_cls").reshape(1, H).expand(B, H).contiguous()
+        self.xcache[:, 0] = eng.embed_generic("property_encoder.", cp, cls, B, 1)
+        self.pred = torch.empty(B, n_props, dtype=torch.float32, device=dev)
+        ep = "property_encoder.embeddings."
+        self.emb = dict(pe_w=P.w("property_embed.weight").reshape(H), pe_b=P.w("property_embed.bias"), pos=P.w(ep + "position_embeddings.weight"),
+                        type0=P.w(ep + "token_type_embeddings.weight")[0], gamma=P.w(ep + "LayerNorm.weight"), beta=P.w(ep + "LayerNorm.bias"),
+                        eps=cp.layer_norm_eps)
+
+    @torch.no_grad()
+    def step(self, i: int):
+        """Property i of every molecule from the prefix [CLS, p_0 .. p_{i-1}] held by the cache -> pred[:, i]; appends prefix row i + 1."""
+        from .engine import Batch, Group, SelfKV
+        ops, eng, P, ct, cp, B, H = self.ops, self.eng, self.P, self.ct, self.cp, self.B, self.H
+        n, f, nl = i + 1, ct.fusion_layer, ct.num_hidden_layers
+        x = ops.gather_rows(eng._new(B * n, H), self.xcache.view(B * self.Lc, H), self.idx[self.off[i]:self.off[i + 1]])
+        pv, _, _ = eng.stack_fwd("property_encoder.", cp, range(cp.num_hidden_layers), False, x, Batch([Group(0, B, n, None, B)]), False)
+        g_lo = Batch([Group(0, B, n, None, 0, kv_mask=self.kv_mask).bind(self.src, self.ar, 0)])
+        y, _, _ = eng.stack_fwd(self.TP, ct, range(f, nl - 1), True, pv, g_lo, False)
+        # the last fusion layer on the B last-position rows (a causal query at position n - 1 sees every key of its sequence)
+        xt = ops.gather_rows(eng._new(B, H), y, self.last[i])
+        g_top = Batch([Group(0, B, 1, None, B, kv_mask=self.kv_mask, self_src=SelfKV(y), skv_row0=self.row0[i], skv_len=self.lens[i],
+                             skv_L=n).bind(self.src, self.ar, 0)])
+        yt, _, _ = eng._layer_fwd(f"{self.TP}encoder.layer.{nl - 1}.", ct, True, xt, g_top, False)
+        h, _ = eng._transform_fwd("property_mtr_head.0", "property_mtr_head.2", yt, False, eps=ct.layer_norm_eps, pre=False)
+        ops.s2p_append(h, P.w("property_mtr_head.3.weight").reshape(H), P.w("property_mtr_head.3.bias"), self.pred, i, n_props=self.n_props,
+                       xcache=self.xcache, **self.emb)
+
+
+@torch.no_grad()
+def predict_properties(model, text_ids: torch.Tensor, text_mask: torch.Tensor, n_props: int = 53) -> torch.Tensor:
+    """`smiles_to_pv` (same arguments, same [B, n_props] normalised result) on the engine: S2PDecoder.  A model without an engine -- the
+    CPU oracle, any foreign module exposing the reference's sub-module API -- goes through `smiles_to_pv` itself."""
+    if not hasattr(model, "engine"):
+        return smiles_to_pv(model, text_ids, text_mask, n_props)
+    dec = S2PDecoder(model, text_ids, text_mask, n_props)
+    for i in range(n_props):
+        dec.step(i)
+    return dec.pred
+
+
 def _decode_graphed(dec: "CachedDecoder", book: BeamBook, ids: torch.Tensor, N: int, k: int, max_steps: int, sync_every: int):
     """The loop of beam_search_batched with every step-dependent scalar in device memory: two eager positions (they also set the
     kernels' one-time attributes), then one captured position replayed for the rest."""

@@ -46,8 +46,11 @@ class KVSource:
     packed row).  Each consumer group registers its sequence -> source map; K/V are projected once per layer, and in backward
     the consumers' dK/dV are folded onto the unique rows (CSR inverse map) before the weight- and data-gradient GEMMs."""
 
-    def __init__(self, kv: torch.Tensor, U: int, Lkv: int, row0=None, length=None, pack_idx=None):
+    def __init__(self, kv: torch.Tensor, U: int, Lkv: int, row0=None, length=None, pack_idx=None, proj=None):
         self.kv, self.U, self.Lkv, self.row0, self.len, self.pack_idx = kv, U, Lkv, row0, length, pack_idx
+        # inference over many passes against ONE source (decode.S2PDecoder): {cross-attention prefix: projected keys | values [rows, 2H]},
+        # projected once by the caller; a block whose prefix is listed reads them instead of projecting `kv` again
+        self.proj = proj
         self._idx: List[torch.Tensor] = []
         self.nseq = 0
         self.start = self.list = None
@@ -413,8 +416,9 @@ class Engine:
         else:
             sv["Qc"] = Qc = ops.gemm_nt(X, P.wb(pfx + ".self.query.weight"), self._new(X.shape[0], H), bias=P.w(pfx + ".self.query.bias"),
                                         M_dev=groups.rows_dev)
+            done = {id(g.src): g.src.proj[pfx] for g in groups if g.src is not None and g.src.proj and pfx in g.src.proj}
             kv_of = functools.partial(self._xattn_kv, P.fused(pfx + ".self.", ("key", "value"), "weight"),
-                                      P.fused(pfx + ".self.", ("key", "value"), "bias", what="w"), {})
+                                      P.fused(pfx + ".self.", ("key", "value"), "bias", what="w"), done)
             fx = self.opt.fused_xattn
             fused = ((fx is True or fx == "all" or (fx == "nograd" and not save)) and not self._xattn_off and X32 is None
                      and groups.rows_dev is None and all(ops.xattn_supported(H, nH, g.L, g.Lkv) for g in groups))

@@ -396,6 +396,23 @@ def task_head(A, W2, b2, logits, *, kind, target=None, loss=None, gscale=None, d
     return logits
 
 
+def s2p_append(y, w3, b3, pred, i, *, n_props, xcache=None, pe_w=None, pe_b=None, pos=None, type0=None, gamma=None, beta=None, eps=1e-12):
+    """Close step i of the SMILES -> PV loop and open step i + 1 (csrc/heads.hip::s2p_append_kernel): pred[:, i] = y . w3 + b3 in fp32 and,
+    unless i is the last step, xcache[:, i + 1] = LN(pred[:, i] * pe_w + pe_b + pos[i + 1] + type0) * gamma + beta as bf16.
+    y [rows, H] bf16 (row stride free), pred [rows, >= n_props] fp32, xcache [rows, n_props + 1, H] bf16 contiguous."""
+    rows, H = y.shape
+    assert y.dtype == BF16 and y.stride(1) == 1 and pred.dtype == torch.float32 and pred.dim() == 2 and pred.shape[0] == rows and pred.stride(1) == 1
+    assert pred.shape[1] >= n_props
+    vecs = [w3, pe_w, pe_b, type0, gamma, beta]
+    assert all(v is None or (v.dtype == torch.float32 and v.numel() == H and v.is_contiguous()) for v in vecs)
+    assert b3.dtype == torch.float32 and b3.numel() == 1
+    assert xcache is None or (xcache.dtype == BF16 and tuple(xcache.shape) == (rows, n_props + 1, H) and xcache.is_contiguous())
+    assert pos is None or (pos.dtype == torch.float32 and pos.is_contiguous() and pos.shape[0] >= n_props + 1 and pos.shape[1] == H)
+    _call("spmm_s2p_append", _p(y), _row_stride(y), _p(w3), _p(b3), _p(pe_w), _p(pe_b), _p(pos), _p(type0), _p(gamma), _p(beta), float(eps),
+          _p(pred), _row_stride(pred), _p(xcache), rows, H, int(n_props), int(i), _st())
+    return pred
+
+
 def rows_linear(x, W, bias, out, *, act=0):
     """out[r,n] = act(bias[n] + x[r,:] . W[n,:]) in fp32; x [rows, K] fp32 or bf16 (row stride free), W [N, K] fp32 contiguous."""
     rows, K = x.shape
