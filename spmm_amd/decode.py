@@ -11,8 +11,10 @@ from typing import List, Tuple
 import numpy as np
 import torch
 
+from . import ops                # (reached as module attributes at call time: bench.py wraps ops.gemm_nt, ops.decode_attn, ops.ln_fwd)
+
 CLS_ID, SEP_ID = 2, 3           # vocab_bpe_300.txt:3-4
-GRAPH_BELOW_ROWS = 200          # beam rows below which one hipGraph replay per position is the default: with the bookkeeping in one launch a position is a
+GRAPH_BELOW_ROWS = 200          # measured break-even of graph=True, not a switch (replay is opt-in): with the bookkeeping in one launch a position is a
 #                                 chain of ~130 dependent kernels (1.95 ms at 100 rows, 2.2 at 1 000, 3.6 at 5 000) and replay gains 7 % at 100 rows, 2 % at
 #                                 250, nothing from 500 on -- and a replayed graph has a fixed batch: no compaction of finished molecules
 last_run: dict = {}             # what the last eager beam_search_batched did: molecules, compactions, final_batch, positions
@@ -73,6 +75,25 @@ def gumbel_noise_host(seed: int, salt: int, mol_ids, t: int, k: int, V: int, Lma
     return torch.from_numpy(-np.log(-np.log(u))).reshape(-1, V)
 
 
+class _GumbelNoise:
+    """The noise of one seeded search: `noise(t, mol)` -> fp32 [n * k, V] after `t` generated tokens, for the molecules now in the batch
+    (mol: BeamBook.mol, None = all N).  On the device into one buffer where spmm_gumbel_noise takes the shape (k <= 8, V <= 512,
+    Lmax <= 256: whatever the one-launch beam step takes), else the host form -- which only ever serves the whole batch."""
+
+    def __init__(self, seed: int, mol_base: int, N: int, k: int, V: int, Lmax: int, device, on_device: bool):
+        self.seed, self.mol_base, self.N, self.shape, self.device = seed, mol_base, N, (k, V, Lmax), device
+        self.buf = torch.empty(N * k, V, dtype=torch.float32, device=device) if on_device else None
+        if on_device:
+            self.seed_dev = torch.tensor([(int(seed) & _M64) - ((int(seed) & (1 << 63)) << 1)], dtype=torch.int64, device=device)
+
+    def __call__(self, t: int, mol: torch.Tensor | None = None) -> torch.Tensor:
+        k, V, Lmax = self.shape
+        if self.buf is None:
+            return gumbel_noise_host(self.seed, GUMBEL_SALT, range(self.mol_base, self.mol_base + self.N), t, k, V, Lmax).to(torch.float32).to(self.device)
+        n = self.N if mol is None else mol.numel()
+        return ops.gumbel_noise(self.seed_dev, n, k, V, Lmax, salt=GUMBEL_SALT, t=t, mol=mol, mol_base=self.mol_base, out=self.buf[:n * k])
+
+
 def _pick_seeded(logits: torch.Tensor, noise: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """The sampled branch of `_pick` with explicit noise, on LOGITS [..., V]: ids = the k largest of logits + noise in descending order,
     log-probs = log_softmax(logits) at those ids (unperturbed) -> (log-probs, ids) [..., k].  The tensor-op twin of the SAMPLED
@@ -99,6 +120,17 @@ def encode_properties(model, prop: torch.Tensor, prop_mask: torch.Tensor | None 
 # ------------------------------------------------------------------------------------------------------------------
 # Batched decoding: N molecules x k beams per launch, key/value cache, no host round trips inside the loop.
 # ------------------------------------------------------------------------------------------------------------------
+def _set_column(x: torch.Tensor, t, v):
+    """x[..., t] = v for a column t on the host (int) or in device memory (int64 [1]: no host read); v: a scalar or a tensor of x's
+    shape without the last dimension."""
+    if isinstance(t, int):
+        x[..., t] = v
+    elif torch.is_tensor(v):
+        x.index_copy_(-1, t, v.unsqueeze(-1))
+    else:
+        x.index_fill_(-1, t, v)
+
+
 class BeamBook:
     """The beam bookkeeping of the reference's search for N independent molecules at once, as tensor ops (no `.item()`):
     per molecule it makes exactly the decisions d_pv2smiles_batched.py:29-57 makes -- candidates ending in [SEP] are moved to
@@ -128,58 +160,37 @@ class BeamBook:
         self.cur_p = values.clone()
         self.t = 2
 
-    def update(self, values: torch.Tensor, indices: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """values/indices [N,k,k]: per live beam the k best next tokens.  Returns (parent [N,k], token [N,k]) of the new beams."""
-        N, k, t, F = self.N, self.k, self.t, self.F
+    def update(self, values: torch.Tensor, indices: torch.Tensor, t: torch.Tensor | None = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """values/indices [N,k,k]: per live beam the k best next tokens.  Returns (parent [N,k], token [N,k]) of the new beams.
+        The number of tokens held by the live beams is self.t, advanced here -- or `t` (int64 [1]) in device memory, self.t then left to
+        the caller: nothing of the call sequence depends on the position (graph replay).  The state is updated in place either way."""
+        N, k, F, L = self.N, self.k, self.F, self.Lmax
+        host = t is None
+        if host:
+            t = self.t
         k2_p = (self.cur_p[:, :, None] + values).reshape(N, k * k)
         idx = indices.reshape(N, k * k)
         ends = (idx == SEP_ID) & ~self.done[:, None]
         e = ends.long()
         slot = torch.where(ends, self.fin_n[:, None] + torch.cumsum(e, 1) - e, torch.full_like(e, F))
         self.fin_p.scatter_(1, slot, k2_p)
-        self.fin_len.scatter_(1, slot, torch.full_like(e, t + 1))
-        cand = self.tokens[:, :, None, :].expand(N, k, k, self.Lmax).reshape(N, k * k, self.Lmax).clone()
-        cand[:, :, t] = SEP_ID
-        self.fin_tok.scatter_(1, slot[:, :, None].expand(N, k * k, self.Lmax), cand)
-        self.fin_n = self.fin_n + e.sum(1)
+        self.fin_len.scatter_(1, slot, e * (t + 1))        # (0 for the candidates that go to the dump slot)
+        cand = self.tokens[:, :, None, :].expand(N, k, k, L).reshape(N, k * k, L).clone()
+        _set_column(cand, t, SEP_ID)
+        self.fin_tok.scatter_(1, slot[:, :, None].expand(N, k * k, L), cand)
+        self.fin_n += e.sum(1)
         k2_p = torch.where(ends, torch.full_like(k2_p, -1e5), k2_p)
         new_p, flat = torch.topk(k2_p, k, dim=1)
         parent = flat // k
         tok = idx.gather(1, flat)
         live = ~(self.done | (self.fin_n >= k))           # a molecule that just reached k finals breaks before this update
-        new_tokens = self.tokens.gather(1, parent[:, :, None].expand(N, k, self.Lmax)).clone()
-        new_tokens[:, :, t] = tok
-        self.tokens = torch.where(live[:, None, None], new_tokens, self.tokens)
-        self.cur_p = torch.where(live[:, None], new_p, self.cur_p)
-        self.done = self.done | (self.fin_n >= k)
-        self.t = t + 1
-        return parent, tok
-
-    def update_dev(self, values: torch.Tensor, indices: torch.Tensor, t64: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """`update` with the number of tokens held by the live beams (t64: int64 [1]) in device memory and every piece of state
-        updated in place, so that the call sequence is identical at every step (graph replay).  Same decisions as `update`."""
-        N, k, F, L = self.N, self.k, self.F, self.Lmax
-        k2_p = (self.cur_p[:, :, None] + values).reshape(N, k * k)
-        idx = indices.reshape(N, k * k)
-        ends = (idx == SEP_ID) & ~self.done[:, None]
-        e = ends.long()
-        slot = torch.where(ends, self.fin_n[:, None] + torch.cumsum(e, 1) - e, torch.full_like(e, F))
-        self.fin_p.scatter_(1, slot, k2_p)
-        self.fin_len.scatter_(1, slot, (t64 + 1).expand(N, k * k).contiguous())
-        cand = self.tokens[:, :, None, :].expand(N, k, k, L).reshape(N, k * k, L).clone()
-        cand.index_fill_(2, t64, SEP_ID)
-        self.fin_tok.scatter_(1, slot[:, :, None].expand(N, k * k, L), cand)
-        self.fin_n.add_(e.sum(1))
-        k2_p = torch.where(ends, torch.full_like(k2_p, -1e5), k2_p)
-        new_p, flat = torch.topk(k2_p, k, dim=1)
-        parent = flat // k
-        tok = idx.gather(1, flat)
-        live = ~(self.done | (self.fin_n >= k))
-        new_tokens = self.tokens.gather(1, parent[:, :, None].expand(N, k, L)).clone()
-        new_tokens.scatter_(2, t64.view(1, 1, 1).expand(N, k, 1), tok[:, :, None])
-        self.tokens.copy_(torch.where(live[:, None, None], new_tokens, self.tokens))
-        self.cur_p.copy_(torch.where(live[:, None], new_p, self.cur_p))
-        self.done.logical_or_(self.fin_n >= k)
+        new_tokens = self.tokens.gather(1, parent[:, :, None].expand(N, k, L))
+        _set_column(new_tokens, t, tok)
+        torch.where(live[:, None, None], new_tokens, self.tokens, out=self.tokens)
+        torch.where(live[:, None], new_p, self.cur_p, out=self.cur_p)
+        self.done |= self.fin_n >= k
+        if host:
+            self.t = t + 1
         return parent, tok
 
     def live_slots(self) -> torch.Tensor:
@@ -230,19 +241,30 @@ class RecomputeDecoder:
     def __init__(self, model, prop_embeds: torch.Tensor, k: int, Lmax: int):
         self.m, self.k = model, k
         self.kv = prop_embeds.repeat_interleave(k, dim=0)
-        self.tok = torch.zeros(self.kv.shape[0], Lmax, dtype=torch.long, device=prop_embeds.device)
+        self.device = prop_embeds.device
+        self.tok = torch.zeros(self.kv.shape[0], Lmax, dtype=torch.long, device=self.device)
 
     def step(self, ids: torch.Tensor, t: int) -> torch.Tensor:
         self.tok[:, t] = ids
         text = self.tok[:, : t + 1]
         return self.m.text_encoder(text, attention_mask=torch.ones_like(text), encoder_hidden_states=self.kv,
-                                   encoder_attention_mask=torch.ones(self.kv.shape[:-1], dtype=torch.long, device=self.kv.device),
+                                   encoder_attention_mask=torch.ones(self.kv.shape[:-1], dtype=torch.long, device=self.device),
                                    return_dict=True, is_decoder=True, return_logits=True)[:, -1, :]
 
     def reorder(self, parent: torch.Tensor, t: int):
         N, k = parent.shape
         L = self.tok.shape[1]
         self.tok = self.tok.view(N, k, L).gather(1, parent[:, :, None].expand(N, k, L)).reshape(N * k, L)
+
+
+def _cross_kv(eng, bert_pfx: str, c, rows: torch.Tensor) -> dict:
+    """Keys | values of the cross-attention of every fusion layer, projected once from `rows` (bf16 [M, H]): {layer: bf16 [M, 2H]}."""
+    P, out = eng.P, {}
+    for l in range(c.fusion_layer, c.num_hidden_layers):
+        pf = f"{bert_pfx}encoder.layer.{l}.crossattention.self."
+        out[l] = ops.gemm_nt(rows, P.fused(pf, ("key", "value"), "weight"), eng._new(rows.shape[0], 2 * c.hidden_size),
+                             bias=P.fused(pf, ("key", "value"), "bias", what="w"))
+    return out
 
 
 class CachedDecoder:
@@ -254,37 +276,27 @@ class CachedDecoder:
     def __init__(self, model, prop_embeds: torch.Tensor, k: int, Lmax: int, repeat: int = 1, xkv: dict | None = None):
         """repeat: decode `repeat` molecules per row of prop_embeds (generation of many samples from one PV: the cross-attention keys /
         values are projected once per row and copied).  xkv: the projections of an earlier decoder on the same prop_embeds (`xkv_once`)."""
-        from . import ops
         from .engine import BF
-        self.ops, self.BF = ops, BF
         eng = model.engine
         self.eng, self.P, self.c, self.k = eng, eng.P, model.cfg.text, k
         self.pfx = "text_encoder."
         c, dev = self.c, model.device_
+        self.device = dev
         N, Lkv, H = prop_embeds.shape
         N *= repeat
         assert Lmax <= 256 and H == c.hidden_size and c.hidden_size // c.num_attention_heads == 64
         self.N, self.R, self.Lmax, self.Lp, self.H = N, N * k, Lmax, Lkv, H
-        nl = c.num_hidden_layers
         # head-major cache [R, nH, Lmax, 64]: the positions of a (row, head) are one contiguous 128-B-per-key stream for the wave that reads them
-        self.kc = [torch.empty(self.R, c.num_attention_heads, Lmax, 64, dtype=BF, device=dev) for _ in range(nl)]
-        self.vc = [torch.empty(self.R, c.num_attention_heads, Lmax, 64, dtype=BF, device=dev) for _ in range(nl)]
+        self.kc = [torch.empty(self.R, c.num_attention_heads, Lmax, 64, dtype=BF, device=dev) for _ in range(c.num_hidden_layers)]
+        self.vc = [torch.empty(self.R, c.num_attention_heads, Lmax, 64, dtype=BF, device=dev) for _ in range(c.num_hidden_layers)]
         self.anc = torch.arange(self.R, dtype=torch.int32, device=dev)[:, None].repeat(1, Lmax).contiguous()
         self.rows = torch.arange(self.R, dtype=torch.int32, device=dev)
+        self.cols = torch.arange(Lmax, device=dev)
         self.rowmap = None                               # after compact(): cache row of every beam row still decoded (None: the row itself)
         if xkv is None:
-            kv_src = prop_embeds.to(dev).to(BF).reshape(-1, H).contiguous()
-            xkv = {}
-            for l in range(c.fusion_layer, nl):
-                pf = f"{self.pfx}bert.encoder.layer.{l}.crossattention.self."
-                KV = torch.empty(kv_src.shape[0], 2 * H, dtype=BF, device=dev)
-                ops.gemm_nt(kv_src, self.P.fused(pf, ("key", "value"), "weight"), KV, bias=self.P.fused(pf, ("key", "value"), "bias", what="w"))
-                xkv[l] = KV
+            xkv = _cross_kv(eng, self.pfx + "bert.", c, prop_embeds.to(dev).to(BF).reshape(-1, H).contiguous())
         self.xkv_once = xkv                              # per row of prop_embeds
         self.xkv = {l: (KV.view(-1, Lkv, 2 * H).repeat_interleave(repeat, dim=0).reshape(-1, 2 * H) if repeat > 1 else KV) for l, KV in xkv.items()}
-
-    def _new(self, *shape, dtype=None):
-        return torch.empty(*shape, dtype=dtype or self.BF, device=self.anc.device)
 
     @torch.no_grad()
     def compact(self, keep: torch.Tensor):
@@ -305,51 +317,45 @@ class CachedDecoder:
         """ids [R]: the token at position t of every beam -> fp32 logits [R, V] for position t + 1.
         t_dev (int32 [1], device): the position comes from device memory instead (t is then ignored), which makes the whole
         launch sequence independent of the step -- capturable once as a hipGraph and replayed (beam_search_batched(graph=True))."""
-        ops, P, c, R, H, nH = self.ops, self.P, self.c, self.R, self.H, self.c.num_attention_heads
+        P, c, R, H, nH, new = self.P, self.c, self.R, self.H, self.c.num_attention_heads, self.eng._new
         bp = self.pfx + "bert."
         # residual sublayers: the engine's (inference: no tape, dropout off -- the row kernel then never reads the seed)
         sub = functools.partial(self.eng._proj_ln, X32=None, save=False, eps=c.layer_norm_eps, ph=0.0, salt=0)
-        x = self._new(R, H)
+        x = new(R, H)
         ops.embed_step_ln_fwd(ids.to(torch.int32).contiguous(), t, x, pos_ptr=t_dev, word=P.w(bp + "embeddings.word_embeddings.weight"),
                               pos=P.w(bp + "embeddings.position_embeddings.weight"), type0=P.w(bp + "embeddings.token_type_embeddings.weight"),
                               gamma=P.w(bp + "embeddings.LayerNorm.weight"), beta=P.w(bp + "embeddings.LayerNorm.bias"), eps=c.layer_norm_eps)
         for l in range(c.num_hidden_layers):
             lp = f"{bp}encoder.layer.{l}."
             pf = lp + "attention."
-            QKV = self._new(R, 3 * H)
+            QKV = new(R, 3 * H)
             ops.gemm_nt(x, P.fused(pf + "self.", ("query", "key", "value"), "weight"), QKV,
                         bias=P.fused(pf + "self.", ("query", "key", "value"), "bias", what="w"))
-            ctx = self._new(R, H)                       # (the launch also moves the new key / value rows into the cache)
+            ctx = new(R, H)                       # (the launch also moves the new key / value rows into the cache)
             ops.decode_attn(QKV[:, :H], self.kc[l], self.vc[l], ctx, nH=nH, Lkv=self.Lmax if t_dev is not None else t + 1,
                             seq_stride=self.Lmax * H, tok_stride=64, head_stride=self.Lmax * 64, anc=self.anc, group=self.k, t_ptr=t_dev, knew=QKV[:, H:2 * H], vnew=QKV[:, 2 * H:],
                             rowmap=self.rowmap)
             a = sub(pf + "output.", ctx, x)[0]
             if l >= c.fusion_layer:
                 pf = lp + "crossattention."
-                q = self._new(R, H)
+                q = new(R, H)
                 ops.gemm_nt(a, P.wb(pf + "self.query.weight"), q, bias=P.w(pf + "self.query.bias"))
                 KV = self.xkv[l]
                 ops.decode_attn(q, KV[:, :H], KV[:, H:], ctx, nH=nH, Lkv=self.Lp, seq_stride=self.Lp * 2 * H, tok_stride=2 * H, kv_div=self.k, group=self.k)
                 a = sub(pf + "output.", ctx, a)[0]
-            h = self._new(R, c.intermediate_size)
+            h = new(R, c.intermediate_size)
             ops.gemm_nt(a, P.wb(lp + "intermediate.dense.weight"), h, bias=P.w(lp + "intermediate.dense.bias"), epi=ops.EPI_GELU)
             x = sub(lp + "output.", h, a)[0]
         logits, _ = self.eng.lm_head_fwd(self.pfx, c, x, False)
         return logits
 
     @torch.no_grad()
-    def reorder(self, parent: torch.Tensor, t: int):
-        """New beam b of molecule n continues old beam parent[n, b]; positions < t are inherited, position t is its own."""
+    def reorder(self, parent: torch.Tensor, t):
+        """New beam b of molecule n continues old beam parent[n, b]; positions < t are inherited, position t and everything behind it
+        is its own.  t: int, or int64 [1] in device memory (graph replay).  The table is updated in place: its address is static."""
         N, k, L = self.N, self.k, self.Lmax
-        self.anc = self.anc.view(N, k, L).gather(1, parent[:, :, None].expand(N, k, L)).reshape(N * k, L).contiguous()
-        self.anc[:, t:] = self.rows[:, None]
-
-    @torch.no_grad()
-    def reorder_dev(self, parent: torch.Tensor, t_next64: torch.Tensor):
-        """`reorder` with the next position in device memory and the table updated in place (static address for graph replay)."""
-        N, k, L = self.N, self.k, self.Lmax
-        self.anc.copy_(self.anc.view(N, k, L).gather(1, parent[:, :, None].expand(N, k, L)).reshape(N * k, L))
-        self.anc.index_copy_(1, t_next64, self.rows[:, None])
+        anc = self.anc.view(N, k, L).gather(1, parent[:, :, None].expand(N, k, L)).reshape(N * k, L)
+        torch.where(self.cols >= t, self.rows[:, None], anc, out=self.anc)
 
 
 @torch.no_grad()
@@ -368,8 +374,10 @@ def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int =
     the same draws whatever batch it is decoded in, the search runs on the one-launch beam step under the same conditions as the
     deterministic one, and finished molecules are dropped (`compact`) as they are there.
     graph=True (cached, deterministic) captures one decode position -- ~230 launches -- as a hipGraph and replays it: the per-position
-    host cost drops from ~2.3 ms of launch overhead to one graph launch, which is what small batches are bound by.  graph=None (default):
-    replay when the batch is launch-bound -- fewer than GRAPH_BELOW_ROWS beam rows -- and the search is deterministic.  A sampled search
+    host cost drops from ~2.3 ms of launch overhead to one graph launch, which is what small batches are bound by.  Replay is opt-in:
+    graph=None (default) and graph=False are the eager loop.  Every call re-captures its launches (a graph is tied to this call's buffers),
+    capture is process-global on the capture stream's device -- another thread touching the GPU meanwhile aborts it -- and a replayed
+    graph cannot drop finished molecules; it gains 7 % at 100 beam rows and nothing from 500 on (GRAPH_BELOW_ROWS).  A sampled search
     (seeded or not) stays eager whatever `graph` says.  compact=True (eager fused path): finished
     molecules are dropped from the batch as the search goes (same results; the reference decodes one molecule at a time and simply stops)."""
     if cached is None:
@@ -378,84 +386,77 @@ def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int =
     if cached:
         model.engine.train_mode = False
     dec = (CachedDecoder if cached else RecomputeDecoder)(model, prop_embeds, k, max_steps + 3)
-    return _search(model, dec, prop_embeds.shape[0], k, max_steps, cached, sync_every, stochastic, generator, graph, compact, seed, mol_base)
+    return _search(model, dec, prop_embeds.shape[0], k=k, max_steps=max_steps, sync_every=sync_every, stochastic=stochastic, generator=generator,
+                   graph=bool(graph), compact=compact, seed=seed, mol_base=mol_base)
 
 
-def _search(model, dec, N: int, k: int, max_steps: int, cached: bool, sync_every: int, stochastic: bool, generator, graph, compact: bool,
-            seed: int | None, mol_base: int):
+def _advance(dec, book: BeamBook, ids: torch.Tensor, t: int, *, t_dev: torch.Tensor | None = None, noise=None, pick=None,
+             ids_out: torch.Tensor | None = None) -> torch.Tensor:
+    """One position of the search: the tokens `ids` at position t of every beam row -> the tokens at position t + 1, with the book and the
+    decoder's ancestry brought up to date -- by the one-launch beam step (book.fused) or by pick, BeamBook.update and reorder.
+    t_dev (int32 [1], device; cached decoder): the position comes from device memory in every launch and t is ignored, so the call can
+    be captured once and replayed.  noise: the seeded search's source (_GumbelNoise).  pick(logits [N, k, V], noise) -> (log-probs, ids)
+    [N, k, k]: the candidates of the tensor-op form (None: the k most probable).  ids_out: static buffer that receives the result."""
+    logits = dec.step(ids, t) if t_dev is None else dec.step(ids, t, t_dev=t_dev)
+    noise = None if noise is None else noise(t, book.mol)
+    if book.fused:
+        return book.step_fused(logits, dec.anc, t_ptr=t_dev, t_off=0 if t_dev is None else 1, ids_out=ids_out, rowmap=dec.rowmap, noise=noise)
+    logits = logits.view(book.N, book.k, -1).float()
+    values, indices = _pick(torch.softmax(logits, dim=-1), book.k, False) if pick is None else pick(logits, noise)
+    held = None if t_dev is None else t_dev.to(torch.int64) + 1          # tokens held by every live beam (host: book.t = t + 1)
+    parent, tok = book.update(values, indices, held)
+    dec.reorder(parent, t + 1 if held is None else held)
+    ids = tok.reshape(-1)
+    return ids if ids_out is None else ids_out.copy_(ids)
+
+
+def _search(model, dec, N: int, *, k: int, max_steps: int, sync_every: int = 4, stochastic: bool = False, generator=None, graph: bool = False,
+            compact: bool = True, seed: int | None = None, mol_base: int = 0):
     """beam_search_batched behind the decoder's construction (generate_with_property builds its decoders from one encoded PV)."""
     last_run.clear()
-    if graph is None:
-        # Replay is OPT-IN (graph=True) since round 5: every call re-captures its ~130 kernels (a graph is tied to this call's buffers), capture
-        # is process-global on the capture stream's device -- another thread touching the GPU meanwhile aborts it -- and a replayed graph
-        # cannot drop finished molecules (`compact`).  It gains 7 % at 100 beam rows and nothing from 500 on (GRAPH_BELOW_ROWS).
-        graph = False
-    dev = dec.anc.device if cached else dec.kv.device
-    Lmax = max_steps + 3
+    cached, dev = isinstance(dec, CachedDecoder), dec.device
+    ids = torch.full((N * k,), CLS_ID, dtype=torch.long, device=dev)
+    logits = dec.step(ids, 0).view(N, k, -1)[:, 0].float()              # all k rows hold the same [CLS] prefix
+    Lmax, V = max_steps + 3, logits.shape[-1]
     seeded = bool(stochastic and seed is not None)
     # one launch per position for the beam bookkeeping (csrc/decode.hip::beam_step_kernel: k <= 8 beams, vocabulary <= 512, histories <= 256
-    # tokens -- the tensor-op bookkeeping serves everything else)
-    fused = bool(cached and (seeded or not stochastic) and k <= 8 and FUSED_BEAM_STEP and model.cfg.text.vocab_size <= 512 and Lmax <= 256)
-    book = BeamBook(N, k, max_steps, dev, fused=fused)
-    ids = torch.full((N * k,), CLS_ID, dtype=torch.long, device=dev)
-    logits = dec.step(ids, 0).view(N, k, -1)[:, 0]                       # all k rows hold the same [CLS] prefix
-    if seeded:
-        V = logits.shape[-1]
-        dev_noise = bool(cached and k <= 8 and V <= 512 and Lmax <= 256)          # (what spmm_gumbel_noise accepts; else the host form)
-        if dev_noise:
-            from . import ops
-            seed_dev = torch.tensor([(int(seed) & _M64) - ((int(seed) & (1 << 63)) << 1)], dtype=torch.int64, device=dev)
-            nbuf = torch.empty(N * k, V, dtype=torch.float32, device=dev)
+    # tokens -- the tensor-op bookkeeping serves everything else); spmm_gumbel_noise accepts the same shapes
+    fits = bool(cached and k <= 8 and model.cfg.text.vocab_size <= 512 and Lmax <= 256)
+    book = BeamBook(N, k, max_steps, dev, fused=bool(fits and FUSED_BEAM_STEP and (seeded or not stochastic)))
+    noise_at = _GumbelNoise(seed, mol_base, N, k, V, Lmax, dev, on_device=fits) if seeded else None
 
-        def noise_at(t: int, n_cur: int) -> torch.Tensor:
-            """fp32 [n_cur*k, V] for the molecules now in the batch, after `t` generated tokens"""
-            if dev_noise:
-                return ops.gumbel_noise(seed_dev, n_cur, k, V, Lmax, salt=GUMBEL_SALT, t=t, mol=book.mol, mol_base=mol_base, out=nbuf[:n_cur * k])
-            return gumbel_noise_host(seed, GUMBEL_SALT, range(mol_base, mol_base + N), t, k, V, Lmax).to(torch.float32).to(dev)
+    def pick(logits, noise):
+        return _pick_seeded(logits, noise, k) if seeded else _pick(torch.softmax(logits, dim=-1), k, stochastic, generator)
 
-        values, indices = _pick_seeded(logits.float(), noise_at(0, N).view(N, k, V)[:, 0], k)
-    else:
-        values, indices = _pick(torch.softmax(logits.float(), dim=-1), k, stochastic, generator)
+    values, indices = pick(logits, noise_at(0).view(N, k, -1)[:, 0] if seeded else None)
     book.first(values, indices)
     ids = indices.reshape(N * k)
     if graph and cached and not stochastic:
-        return _decode_graphed(dec, book, ids, N, k, max_steps, sync_every)
+        return _decode_graphed(dec, book, ids, max_steps, sync_every)
     n_cur = N
     last_run.update(molecules=N, compactions=0, final_batch=N, positions=0)
     for s in range(max_steps):
-        logits = dec.step(ids, s + 1)
-        if fused:
-            ids = book.step_fused(logits, dec.anc, rowmap=dec.rowmap, noise=noise_at(s + 1, n_cur) if seeded else None)
-        else:
-            if seeded:
-                values, indices = _pick_seeded(logits.view(N, k, -1).float(), noise_at(s + 1, N), k)
-            else:
-                values, indices = _pick(torch.softmax(logits.view(N, k, -1).float(), dim=-1), k, stochastic, generator)
-            parent, tok = book.update(values, indices)
-            dec.reorder(parent, s + 2)
-            ids = tok.reshape(N * k)
-        if s % sync_every == sync_every - 1:
-            if not fused:
-                if book.all_done():
-                    last_run["positions"] = s + 1
-                    break
-                continue
-            n_live = N - int(book.n_done.item())         # the one host read of the loop
-            if n_live == 0:
-                last_run["positions"] = s + 1
-                break
-            if compact:
-                # molecules that hold their k finals stop costing anything: once a quarter of the batch is done the rest is gathered into
-                # a smaller batch (caches stay where they are, CachedDecoder.compact)
-                if n_live <= COMPACT_BELOW * n_cur and n_cur - n_live >= 4:
-                    keep = book.live_slots()
-                    dec.compact(keep)
-                    book.compact(keep)
-                    ids = ids.view(n_cur, k)[keep].reshape(-1).contiguous()
-                    n_cur = int(keep.numel())
-                    last_run["compactions"] += 1
-                    last_run["final_batch"] = n_cur
+        ids = _advance(dec, book, ids, s + 1, noise=noise_at, pick=pick)
         last_run["positions"] = s + 1
+        if s % sync_every != sync_every - 1:
+            continue
+        if not book.fused:
+            if book.all_done():
+                break
+            continue
+        n_live = N - int(book.n_done.item())         # the one host read of the loop
+        if n_live == 0:
+            break
+        # molecules that hold their k finals stop costing anything: once a quarter of the batch is done the rest is gathered into
+        # a smaller batch (caches stay where they are, CachedDecoder.compact)
+        if compact and n_live <= COMPACT_BELOW * n_cur and n_cur - n_live >= 4:
+            keep = book.live_slots()
+            dec.compact(keep)
+            book.compact(keep)
+            ids = ids.view(n_cur, k)[keep].reshape(-1).contiguous()
+            n_cur = int(keep.numel())
+            last_run["compactions"] += 1
+            last_run["final_batch"] = n_cur
     return book.results()
 
 
@@ -484,7 +485,7 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
             xkv = dec.xkv_once
         else:
             dec = RecomputeDecoder(model, prop_embeds.expand(n, -1, -1), k, max_steps + 3)
-        res = _search(model, dec, n, k, max_steps, cached, 4, stochastic, None, False, True, seed if stochastic else None, base)
+        res = _search(model, dec, n, k=k, max_steps=max_steps, stochastic=stochastic, seed=seed if stochastic else None, mol_base=base)
         for finals in res:
             if not finals:
                 none += 1
@@ -537,13 +538,12 @@ class S2PDecoder:
 
     @torch.no_grad()
     def __init__(self, model, text_ids: torch.Tensor, text_mask: torch.Tensor, n_props: int = 53):
-        from . import ops
-        from .engine import BF, Batch, Group, KVSource
+        from .engine import BF, KVSource, host_token_count
         eng = model.engine
         eng.train_mode = False
-        self.ops, self.eng, self.P, self.ct, self.cp = ops, eng, eng.P, model.cfg.text, model.cfg.prop
+        self.eng, self.P, self.ct, self.cp = eng, eng.P, model.cfg.text, model.cfg.prop
         ct, cp, P, dev = self.ct, self.cp, eng.P, model.device_
-        H, f, nl = ct.hidden_size, ct.fusion_layer, ct.num_hidden_layers
+        H, f = ct.hidden_size, ct.fusion_layer
         B, Lt = text_ids.shape
         Lc = n_props + 1
         if Lc > cp.max_position_embeddings:
@@ -552,27 +552,14 @@ class S2PDecoder:
             raise ValueError(f"sequence length {Lt} exceeds the {ct.max_position_embeddings} position embeddings")
         self.B, self.n_props, self.Lc, self.H = B, n_props, Lc, H
         # ---- the text, once: embeddings, packed rows, unimodal layers
-        n_tokens = None
-        if text_mask.device.type == "cpu":               # a host mask of non-empty prefixes sizes the packed batch without a device read
-            lens = text_mask.sum(1)
-            if bool((lens > 0).all()) and bool(((torch.arange(Lt)[None, :] < lens[:, None]) == (text_mask != 0)).all()):
-                n_tokens = int(lens.sum())
         ids32 = text_ids.to(dev).to(torch.int32).contiguous()
         mask32 = text_mask.to(dev).to(torch.int32).contiguous()
         x, _ = eng.embed_text(self.TP, ct, ids32, B, Lt, False)
-        pk = eng._pack_plan(mask32, B, Lt, n_tokens) if (eng.pack_text and Lt <= ops.ATTN_MAXL) else None
-        if pk:
-            x = ops.gather_rows2(eng._new(pk["M"], H), x, pk["rows"])
-            g = Batch([Group(0, B, Lt, None, B, q_row0=pk["row0"], q_len=pk["len"], nrows=pk["M"])])
-        else:
-            g = Batch([Group(0, B, Lt, mask32, B)])
+        pk = eng._pack_plan(mask32, B, Lt, host_token_count(text_mask)) if (eng.pack_text and Lt <= ops.ATTN_MAXL) else None
+        x, g, _ = eng.text_rows(x, mask32, pk)
         text, _, _ = eng.stack_fwd(self.TP, ct, range(0, f), False, x, g, False)
         # ---- cross-attention keys | values of every fusion layer, once
-        proj = {}
-        for l in range(f, nl):
-            pf = f"{self.TP}encoder.layer.{l}.crossattention"
-            proj[pf] = ops.gemm_nt(text, P.fused(pf + ".self.", ("key", "value"), "weight"), eng._new(text.shape[0], 2 * H),
-                                   bias=P.fused(pf + ".self.", ("key", "value"), "bias", what="w"))
+        proj = {f"{self.TP}encoder.layer.{l}.crossattention": KV for l, KV in _cross_kv(eng, self.TP, ct, text).items()}
         self.src = KVSource(text, B, Lt, row0=pk["row0"], length=pk["len"], proj=proj) if pk else KVSource(text, B, Lt, proj=proj)
         self.kv_mask = None if pk else mask32            # (packed: the source's lengths are the key mask)
         self.ar = torch.arange(B, dtype=torch.int32, device=dev)
@@ -599,7 +586,7 @@ class S2PDecoder:
     def step(self, i: int):
         """Property i of every molecule from the prefix [CLS, p_0 .. p_{i-1}] held by the cache -> pred[:, i]; appends prefix row i + 1."""
         from .engine import Batch, Group, SelfKV
-        ops, eng, P, ct, cp, B, H = self.ops, self.eng, self.P, self.ct, self.cp, self.B, self.H
+        eng, P, ct, cp, B, H = self.eng, self.P, self.ct, self.cp, self.B, self.H
         n, f, nl = i + 1, ct.fusion_layer, ct.num_hidden_layers
         x = ops.gather_rows(eng._new(B * n, H), self.xcache.view(B * self.Lc, H), self.idx[self.off[i]:self.off[i + 1]])
         pv, _, _ = eng.stack_fwd("property_encoder.", cp, range(cp.num_hidden_layers), False, x, Batch([Group(0, B, n, None, B)]), False)
@@ -627,23 +614,14 @@ def predict_properties(model, text_ids: torch.Tensor, text_mask: torch.Tensor, n
     return dec.pred
 
 
-def _decode_graphed(dec: "CachedDecoder", book: BeamBook, ids: torch.Tensor, N: int, k: int, max_steps: int, sync_every: int):
+def _decode_graphed(dec: CachedDecoder, book: BeamBook, ids: torch.Tensor, max_steps: int, sync_every: int):
     """The loop of beam_search_batched with every step-dependent scalar in device memory: two eager positions (they also set the
     kernels' one-time attributes), then one captured position replayed for the rest."""
-    dev = ids.device
-    ids_s = ids.to(torch.int32).clone() if book.fused else ids.clone()      # static input of the graph
-    t_dev = torch.ones(1, dtype=torch.int32, device=dev)         # position of the token in ids_s
+    ids_s = ids.to(torch.int32).clone() if book.fused else ids.clone()      # static: the position's output is the next position's input
+    t_dev = torch.ones(1, dtype=torch.int32, device=ids.device)  # position of the token in ids_s
 
     def one_position():
-        logits = dec.step(ids_s, 0, t_dev=t_dev)
-        if book.fused:
-            book.step_fused(logits, dec.anc, t_ptr=t_dev, t_off=1, ids_out=ids_s)      # ids_s: the kernel's output and the next position's input
-        else:
-            t64 = t_dev.to(torch.int64)
-            values, indices = _pick(torch.softmax(logits.view(N, k, -1).float(), dim=-1), k, False)
-            parent, tok = book.update_dev(values, indices, t64 + 1)
-            dec.reorder_dev(parent, t64 + 1)
-            ids_s.copy_(tok.reshape(N * k))
+        _advance(dec, book, ids_s, 0, t_dev=t_dev, ids_out=ids_s)
         t_dev.add_(1)
 
     eager = min(2, max_steps)

@@ -170,6 +170,17 @@ class HeadTape:
     ln: LnTape
 
 
+def host_token_count(mask) -> Optional[int]:
+    """Valid-token count of a host mask whose rows are non-empty prefixes (what padding='longest' gives): sizes the packed layers
+    (Engine._pack_plan's `n_tokens`) without a device read.  None for a device mask or another shape of mask (the pack plan then reads
+    the count back itself)."""
+    if not (torch.is_tensor(mask) and mask.device.type == "cpu" and mask.dim() == 2):
+        return None
+    lens = mask.sum(1)
+    prefix = bool((lens > 0).all()) and bool(((torch.arange(mask.shape[1])[None, :] < lens[:, None]) == (mask != 0)).all())
+    return int(lens.sum()) if prefix else None
+
+
 STREAM_TOKENS_MAX = 49152         # B x Lt above which the step runs on one stream (Engine._one_stream)
 
 
@@ -356,6 +367,16 @@ class Engine:
             return None
         # valid rows first, original order kept; whatever the hint was, no index leaves the M rows it sized (csrc/plan.hip)
         return ops.pack_plan(mask32, M, self.hint_bad)
+
+    def text_rows(self, x: torch.Tensor, mask32: torch.Tensor, pk: Optional[dict]):
+        """The embedded text x (dense [B*L, H]) as ONE group of B sequences for the text layers -> (rows, Batch, int64 [B]: the row of
+        position 0 of every sequence): the valid rows of the pack plan `pk` (padding rows dropped), or -- pk None -- the dense rows
+        under their key mask."""
+        B, L = mask32.shape
+        if not pk:
+            return x, Batch([Group(0, B, L, mask32, B)]), torch.arange(B, dtype=torch.int64, device=self.dev) * L
+        x = ops.gather_rows2(self._new(pk["M"], x.shape[1]), x, pk["rows"])
+        return x, Batch([Group(0, B, L, None, B, q_row0=pk["row0"], q_len=pk["len"], nrows=pk["M"])]), pk["row0_64"]
 
     # ---------------------------------------------------------------------------------------- attention block
     def _ln_res(self, x, X, X32, gamma, beta, y, md, **kw):

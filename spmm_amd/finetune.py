@@ -17,6 +17,7 @@ from torch import nn
 
 from . import ops
 from .config import BertConfig, SPMMConfig, finetune_spec, is_buffer
+from .engine import host_token_count
 from .finetune_step import FinetuneStep
 from .model import _CosineSchedule, _FusedAdamW
 from .options import EngineOptions
@@ -126,7 +127,7 @@ class _FinetuneModel(nn.Module):
             return logits[:, 0].clone() if self.TASK == "regression" else logits.clone()
         eng.train_mode = self.training
         if n_tokens is None:
-            n_tokens = _host_tokens(text_attention_mask)
+            n_tokens = host_token_count(text_attention_mask)
         if torch.is_grad_enabled():
             return _FinetuneStepFn.apply(self, ids, mask, value, n_tokens, *[self._parameters[n] for n in self._param_names])
         loss, _ = eng.forward(ids, mask, value, save=False, n_tokens=n_tokens)
@@ -162,7 +163,7 @@ class _FinetuneModel(nn.Module):
         eng.train_mode = self.training
         eng.gscale.fill_(1.0)
         if n_tokens is None:
-            n_tokens = _host_tokens(mask)
+            n_tokens = host_token_count(mask)
         ops.zero_(self.store.grad)
         loss, _ = eng.forward(eng.to_device(ids), eng.to_device(mask), value, n_tokens=n_tokens)
         eng.backward()
@@ -222,16 +223,6 @@ class _FinetuneModel(nn.Module):
                   global_step=int(self.global_step))
         ck.update(extra)
         torch.save(ck, path)
-
-
-def _host_tokens(mask) -> Optional[int]:
-    """Valid-token count of a host mask whose rows are non-empty prefixes (what padding='longest' gives): sizes the packed layers
-    without a device read.  None for a device mask or another shape of mask (the pack plan then reads the count back itself)."""
-    if not (torch.is_tensor(mask) and mask.device.type == "cpu" and mask.dim() == 2):
-        return None
-    lens = mask.sum(1)
-    prefix = bool((lens > 0).all()) and bool(((torch.arange(mask.shape[1])[None, :] < lens[:, None]) == (mask != 0)).all())
-    return int(lens.sum()) if prefix else None
 
 
 class SPMMRegressor(_FinetuneModel):

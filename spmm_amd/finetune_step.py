@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .engine import Batch, Engine, Group
+from .engine import Engine
 
 PFX = "text_encoder.bert."
 TASK_KIND = {"regression": ops.TASK_MSE, "classification": ops.TASK_CE, "multilabel": ops.TASK_BCE}
@@ -45,14 +45,7 @@ class FinetuneStep(Engine):
         pk = self._pack_plan(mask32, B, L, n_tokens) if (self.pack_text and L <= ops.ATTN_MAXL) else None
         if n_tokens is not None:
             self.nan_flag.bitwise_or_(self.hint_bad)       # a wrong hint: the optimiser step becomes a no-op (step.py)
-        if pk:
-            M = pk["M"]
-            x = ops.gather_rows2(self._new(M, H), x, pk["rows"])
-            groups = Batch([Group(0, B, L, None, B, q_row0=pk["row0"], q_len=pk["len"], nrows=M)])
-            cls_idx = pk["row0_64"]
-        else:
-            groups = Batch([Group(0, B, L, mask32, B)])
-            cls_idx = torch.arange(B, dtype=torch.int64, device=self.dev) * L
+        x, groups, cls_idx = self.text_rows(x, mask32, pk)
         y, tape, _ = self.stack_fwd(PFX, c, range(0, f), False, x, groups, save)
         cls = ops.gather_rows2(self._new(B, H), y, cls_idx)
         W2 = P.w("reg_head.2.weight")

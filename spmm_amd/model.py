@@ -17,6 +17,7 @@ from torch import nn
 
 from . import ops
 from .config import SPMMConfig, is_buffer, student_of
+from .engine import host_token_count
 from .options import EngineOptions
 
 try:                                    # the reference subclasses pl.LightningModule (SPMM_models.py:16); keep that when it is importable
@@ -529,12 +530,10 @@ class SPMM(_Base):
             self._grad_sync = grad_sync_fn(self.store, self.options) or False
         n_tokens = draws.get("n_tokens")
         if torch.is_tensor(mask) and mask.device.type == "cpu":       # a host mask (the tokenizer's): count / verify it here, for free
-            lens = mask.sum(1)
-            prefix = bool((lens > 0).all()) and bool(((torch.arange(mask.shape[1])[None, :] < lens[:, None]) == (mask != 0)).all())
-            if n_tokens is not None and (not prefix or int(n_tokens) != int(lens.sum())):
-                raise ValueError(f"n_tokens={n_tokens} contradicts the attention mask (sum {int(lens.sum())}, prefix rows: {prefix})")
-            if n_tokens is None and prefix:
-                n_tokens = int(lens.sum())
+            count = host_token_count(mask)
+            if n_tokens is not None and count != int(n_tokens):
+                raise ValueError(f"n_tokens={n_tokens} contradicts the attention mask (sum {int(mask.sum())}, prefix rows: {count is not None})")
+            n_tokens = count
         losses = self.fused_step(prop, ids, mask, alpha, grad_sync=self._grad_sync or None, mpm_mask=draws.get("mpm_mask"),
                                  neg_idx=draws.get("neg_idx"), n_tokens=n_tokens)
         if self.global_rank == 0:

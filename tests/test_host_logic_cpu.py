@@ -284,6 +284,71 @@ def test_batched_beam_bookkeeping_matches_sequential_search():
         assert n_nonempty >= (6 if steps > 1 else 0), (k, n_nonempty)
 
 
+@pytest.mark.parametrize("k", [1, 2, 5])
+def test_beam_book_update_host_position_equals_device_position(k):
+    """BeamBook.update with the position on the host (self.t, advanced by the call) against the same call sequence with the position as
+    an int64 [1] tensor (what a replayed graph passes; self.t advanced by the caller): state and return values equal bit for bit after
+    every position.  Three molecules, five positions: molecule 0 collects its k finals at the second position, molecule 1 never meets
+    [SEP], molecule 2 meets it at random -- never more than one [SEP] among a beam's candidates, as top-k / sampling without
+    replacement guarantee."""
+    from spmm_amd.decode import SEP_ID, BeamBook
+    N, T, V = 3, 5, 30
+    g = torch.Generator().manual_seed(10 + k)
+    host, dev = BeamBook(N, k, T, "cpu"), BeamBook(N, k, T, "cpu")
+    v0, i0 = torch.log(torch.rand(N, k, generator=g)), torch.randint(4, V, (N, k), generator=g)
+    host.first(v0, i0)
+    dev.first(v0, i0)
+    for s in range(T):
+        values = torch.log(torch.rand(N, k, k, generator=g)).sort(-1, descending=True).values
+        indices = torch.randint(4, V, (N, k, k), generator=g)
+        at = torch.randint(0, k, (k,), generator=g)
+        hit = torch.rand(k, generator=g) < 0.4
+        indices[2, torch.arange(k)[hit], at[hit]] = SEP_ID
+        if s == 1:
+            indices[0, :, 0] = SEP_ID
+        got_h = host.update(values, indices)
+        got_d = dev.update(values, indices, torch.tensor([dev.t]))
+        dev.t += 1
+        assert host.t == dev.t == s + 3
+        for a, b in zip(got_h, got_d):
+            assert torch.equal(a, b), s
+        for name in ("tokens", "cur_p", "fin_p", "fin_len", "fin_tok", "fin_n", "done"):
+            assert torch.equal(getattr(host, name), getattr(dev, name)), (s, name)
+        assert bool(host.done[0]) == (s >= 1) and int(host.fin_n[0]) == (k if s >= 1 else 0)
+    assert not bool(host.done[1]) and int(host.fin_n[1]) == 0
+    assert host.results() == dev.results() and len(host.results()[0]) == k
+
+
+def test_cached_position_launches_the_same_kernels_with_host_and_device_position(dry):
+    """decode._advance, the one position of the eager loop and of the captured graph: with the position on the host and with the position
+    in device memory it issues the same launches in the same order, ending in the one-launch beam step; the tensor-op bookkeeping differs
+    from that only by the missing last launch."""
+    from spmm_amd import decode
+    from spmm_amd.config import tiny_config
+    from spmm_amd.model import SPMM
+    m = SPMM(spmm_config=tiny_config(), no_train=True, device="cpu").eval()
+    N, k, T = 3, 2, 5
+    pe = decode.encode_properties(m, torch.randn(N, 53, generator=torch.Generator().manual_seed(1)))
+    m.engine.train_mode = False
+    logs = {}
+    for fused in (True, False):
+        for where in ("host", "device"):
+            dec, book = decode.CachedDecoder(m, pe, k, T + 3), decode.BeamBook(N, k, T, "cpu", fused=fused)
+            ids = torch.full((N * k,), 5, dtype=torch.int32 if fused else torch.long)
+            book.first(torch.zeros(N, k), torch.full((N, k), 5))
+            dry._dry_log.clear()
+            if where == "host":
+                out = decode._advance(dec, book, ids, 1)
+            else:
+                out = decode._advance(dec, book, ids, 0, t_dev=torch.ones(1, dtype=torch.int32), ids_out=ids)
+                assert out is ids
+            assert tuple(out.shape) == (N * k,)
+            logs[fused, where] = list(dry._dry_log)
+    assert logs[True, "host"] == logs[True, "device"] and logs[False, "host"] == logs[False, "device"]
+    assert logs[True, "host"][-1] == "spmm_beam_step" and logs[True, "host"][:-1] == logs[False, "host"]
+    assert logs[True, "host"].count("spmm_decode_attn") == 2 * tiny_config().text.num_hidden_layers - tiny_config().text.fusion_layer
+
+
 def test_wordpiece_tokenizer_matches_reference_golden(golden_dir):
     """SmilesWordPiece vs ids produced by the WordpieceTokenizer the reference wires into its BertTokenizer, on the
     reference's 300-piece vocabulary (fixture written by oracle/make_tokenizer_golden.py): drug-like SMILES, charged and

@@ -840,7 +840,8 @@ def _peaky_lm(sd, seed=5, sep_gap=1.5):
 def test_cached_decoder_step_matches_full_prefix_forward(env):
     """One-token-per-step decoding against the K/V cache gives the logits the whole-prefix forward (the reference's cost
     model, d_pv2smiles_single.py:26-44) gives for the last position -- through beam reorders that only touch the ancestry
-    table.  Tolerance 3e-2 on log-probabilities (bf16 activations; the two paths use different attention kernels)."""
+    table.  Tolerance 3e-2 on log-probabilities (bf16 activations; the two paths use different attention kernels).  And `reorder` with
+    the position in device memory (what a replayed graph passes) leaves the ancestry table that the host position leaves."""
     O, SPMM, tiny_config, *_ = env
     from spmm_amd import decode
     sd = _peaky_lm(O.closed_form_state_dict(O.tiny_cfg()))
@@ -850,6 +851,7 @@ def test_cached_decoder_step_matches_full_prefix_forward(env):
     props = torch.randn(N, 53, generator=g)
     pe = decode.encode_properties(m, props)
     cached = decode.CachedDecoder(m, pe, k, T + 3)
+    cached_dev = decode.CachedDecoder(m, pe, k, T + 3, xkv=cached.xkv_once)      # (only its ancestry table is used)
     full = decode.RecomputeDecoder(m, pe, k, T + 3)
     ids = torch.full((N * k,), decode.CLS_ID, dtype=torch.long, device="cuda")
     for t in range(T):
@@ -858,8 +860,10 @@ def test_cached_decoder_step_matches_full_prefix_forward(env):
         assert (lc - lf).abs().max().item() < 3e-2, t
         parent = torch.randint(0, k, (N, k), generator=g).cuda()
         cached.reorder(parent, t + 1)
+        cached_dev.reorder(parent, torch.tensor([t + 1], device="cuda"))
         full.reorder(parent, t + 1)
         ids = torch.randint(4, 300, (N * k,), generator=g).cuda()
+    assert torch.equal(cached.anc, cached_dev.anc)
 
 
 def test_batched_cached_beam_search(env):
@@ -877,7 +881,7 @@ def test_batched_cached_beam_search(env):
 
 def test_batched_decode_of_many_molecules_against_the_oracle_search(env):
     """BASELINE configs[3] end to end at a size the CPU yard-stick finishes in seconds: 48 molecules x 5 beams decoded TOGETHER by the
-    K/V-cache decoder (graph replay: the default below 2 500 beam rows) against the fp32 oracle model.  (1) Every hypothesis the
+    K/V-cache decoder (the eager loop: graph replay is opt-in) against the fp32 oracle model.  (1) Every hypothesis the
     decoder returns is scored by the ORACLE, teacher-forced on the same tokens: the log-probability sums agree within 3e-2 per token.
     (2) Against the reference's sequential one-molecule whole-prefix search on the oracle model (oracle/decode_oracle.py), free-running:
     a bf16 near-tie at the k-th candidate may legitimately drop or swap a beam, so the best hypothesis has to be token-for-token equal
@@ -1607,7 +1611,7 @@ def test_graph_replayed_decode_equals_eager(env):
         eager = decode.beam_search_batched(m, props, k=5, max_steps=14, graph=False)
         graphed = decode.beam_search_batched(m, props, k=5, max_steps=14, graph=True)
         runs = [graphed]
-        decode.FUSED_BEAM_STEP = False                # the tensor-op bookkeeping (BeamBook.update / update_dev), eager and replayed
+        decode.FUSED_BEAM_STEP = False                # the tensor-op bookkeeping (BeamBook.update with a host / a device position), eager and replayed
         try:
             runs += [decode.beam_search_batched(m, props, k=5, max_steps=14, graph=False), decode.beam_search_batched(m, props, k=5, max_steps=14, graph=True)]
         finally:
