@@ -171,7 +171,7 @@ int spmm_embed_step_ln_fwd(const int* ids, int pos_index, const int* pos_ptr, co
  * s(r,j) = anc[r*anc_ld + j] (self-attention: beam ancestry table, cache rows are never moved) or r / kv_div when anc is
  * null (cross-attention: the k beams of a molecule share its PV keys/values).  `group` (R % group == 0): rows
  * n*group .. n*group+group-1 are the beams of one molecule -- served by one wave per head (group 2..8), which loads a key row they share once.
- * No mask: beams carry no padding.  t_ptr (optional, device int): the number of valid keys is *t_ptr + 1 (<= Lkv) instead of
+ * No mask: beams carry no padding (a masked, variable-length memory: spmm_decode_xattn).  t_ptr (optional, device int): the number of valid keys is *t_ptr + 1 (<= Lkv) instead of
  * Lkv -- the step counter of a replayed hipGraph.  knew / vnew (optional, with anc; row stride ldn): key and value of the newest
  * position (the last valid one) of every row, straight from the projection output: every row attends ITS OWN newest key / value
  * there (the table's entry for that position must name the row's own cache row: s(r, last) = r, or rowmap[r]), and the launch copies
@@ -181,6 +181,22 @@ int spmm_embed_step_ln_fwd(const int* ids, int pos_index, const int* pos_ptr, co
 int spmm_decode_attn(const void* q, long ldq, const void* K, const void* V, long seq_stride, long tok_stride, long head_stride, const int* anc,
                      int anc_ld, int kv_div, int group, void* out, long ldo, int R, int nH, int Lkv, float scale,
                      const int* t_ptr, const void* knew, const void* vnew, long ldn, const int* rowmap, spmm_stream_t stream);
+
+/* Single-query CROSS-attention over a masked, variable-length memory: the decoder of reaction prediction attends to the encoded reactant
+ * SMILES (SPMM_models_rxn.py `generate`: encoder_hidden_states = text_embeds, encoder_attention_mask = text_mask; xbert.py:305-354 for the
+ * newest position), 1..149 tokens per reaction and different for every reaction of a batch.  Row r (of R) belongs to molecule
+ * n = r / group -- rows n*group .. n*group+group-1 are its beams, served by one wave per head -- whose source is u = kv_seq ? kv_seq[n] : n.
+ * Row r, head h: softmax_j(q_r,h . K[kv_row0[u] + j, h] * scale) V[kv_row0[u] + j, h], j < kv_len[u], head_dim 64.  K / V rows are
+ * token-major with row stride ldkv elements, head h at column h*64: the two halves of the [M, 2H] output of the fused key|value
+ * projection of PACKED text rows (padding rows dropped); a padded [U, L, 2H] buffer is the same call with kv_row0[u] = u*L.
+ * kv_seq (optional, [R/group]), kv_row0, kv_len: device int32.  1 <= kv_len[u] <= Lkv_max <= 256: what the kernel reads from memory is
+ * clamped into that range, so a bad length cannot address outside Lkv_max rows of the source, and no row at or beyond
+ * kv_row0[u] + kv_len[u] is ever read (keys past the end are masked to -inf and not fetched: the last row may end the allocation).
+ * After the caller dropped finished molecules from its batch only kv_seq is gathered; the memory never moves.
+ * 1 <= group <= 8, R % group == 0; ldq, ldo, ldkv multiples of 8, >= nH*64; q, K, V 16-byte aligned, out 8-byte.  Arithmetic and
+ * result layout as spmm_decode_attn (equal lengths give its cross-attention result bit for bit). */
+int spmm_decode_xattn(const void* q, long ldq, const void* K, const void* V, long ldkv, const int* kv_seq, const int* kv_row0,
+                      const int* kv_len, int group, void* out, long ldo, int R, int nH, int Lkv_max, float scale, spmm_stream_t stream);
 
 /* One position of the k-beam PV -> SMILES search for N molecules (d_pv2smiles_batched.py:36-50; the top-k branch of
  * `generate`, d_pv2smiles_single.py:41-44) in one launch.  logits [N*k, V] fp32 (row stride ldl): next-token logits of every beam.
@@ -199,6 +215,16 @@ int spmm_beam_step(const float* logits, long ldl, int N, int k, int V, int Lmax,
                    int* tokens, float* cur_p, float* fin_p, int* fin_len, int* fin_tok, int* fin_n, unsigned char* done,
                    int* anc, int anc_ld, int* ids_out, int* parent_out, int* n_done, const int* mol, const int* rowmap,
                    spmm_stream_t stream);
+
+/* spmm_beam_step with the number of finals that ends a molecule's search as an argument: the arguments of spmm_beam_step, then `need`,
+ * the stream last as everywhere.  A molecule is done once it holds >= need finals; need = k is spmm_beam_step bit for bit, need = k*k is
+ * `evaluate_beam` of reaction prediction (d_rxn_prediction.py), which keeps searching until k*k hypotheses have ended and returns the k
+ * best of them.  k <= need <= k*k and F >= need + k - 1: a position appends at most one [SEP] candidate per beam, so a molecule that is
+ * not done holds < need finals and at most k are added -- slot F, the dump, is never reached. */
+int spmm_beam_step_until(const float* logits, long ldl, int N, int k, int V, int Lmax, int F, int t, const int* t_ptr, int t_off,
+                         int* tokens, float* cur_p, float* fin_p, int* fin_len, int* fin_tok, int* fin_n, unsigned char* done,
+                         int* anc, int anc_ld, int* ids_out, int* parent_out, int* n_done, const int* mol, const int* rowmap,
+                         int need, spmm_stream_t stream);
 
 /* spmm_beam_step for the SAMPLED search (the stochastic branch of `generate`, d_pv2smiles_single.py:38-41): the arguments of spmm_beam_step,
  * then noise [N*k, V] fp32 (row stride ldn >= V), the stream last as everywhere.  The k candidates of a beam are the k largest of

@@ -158,6 +158,20 @@ def finetune_spec(c: BertConfig, task: str, n_output: int = 2) -> List[Spec]:
                 ("reg_head.2.weight", (C, W), "lin_w"), ("reg_head.2.bias", (C,), "lin_b")]
 
 
+def rxn_encoder_config(c_dec: BertConfig) -> BertConfig:
+    """config_bert_smiles.json from config_bert.json: the reactant encoder is the decoder's unimodal half (num_hidden_layers = fusion_layer,
+    so mode='text' runs all of its layers), without cross-attention."""
+    return replace(c_dec, num_hidden_layers=c_dec.fusion_layer, add_cross_attention=False)
+
+
+def rxn_spec(c_dec: BertConfig, c_enc: BertConfig) -> List[Spec]:
+    """Every state_dict entry of the reference's reaction-prediction model, in its order (SPMM_models_rxn.py:12-13): `text_encoder`, the
+    12-layer BertForMaskedLM decoder with cross-attention in the fusion layers, then `text_encoder2`, the BertForMaskedLM that encodes the
+    reactants (its MLM head is part of the state and never used)."""
+    return (_bert_spec("text_encoder.bert.", c_dec, True) + _mlm_spec("text_encoder.", c_dec)
+            + _bert_spec("text_encoder2.bert.", c_enc, False) + _mlm_spec("text_encoder2.", c_enc))
+
+
 MOMENTUM_PAIRS = [("property_encoder.", "property_encoder_m."), ("property_proj.", "property_proj_m."),
                   ("text_encoder.", "text_encoder_m."), ("text_proj.", "text_proj_m.")]   # SPMM_models.py:56-60
 

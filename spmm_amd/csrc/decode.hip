@@ -23,6 +23,8 @@ struct DecAttnP {
   const int* rowmap;            // optional: cache row that row r's newest position is written to (identity when null)
   const bf16* knew; const bf16* vnew; long ldn;   // optional: key / value of the NEWEST position (Lkv - 1) of every row, not yet in the cache: read from
   //                                                 here (row stride ldn) and written to the cache row by the wave that owns the (row, head)
+  const int* kv_seq; const int* kv_row0; const int* kv_len;   // VARLEN (spmm_decode_xattn): the molecule's source u = kv_seq ? kv_seq[n] : n holds its keys /
+  //                                                             values in rows kv_row0[u] .. + kv_len[u] - 1 (row stride tok_stride); Lkv is the largest length allowed
 };
 
 __global__ __launch_bounds__(256) void decode_attn_kernel(DecAttnP p) {
@@ -134,8 +136,13 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 constexpr int DM_SLOT = 4096;           // one block: 16 keys x 128 B of key rows, then 16 x 128 B of value rows
 
 constexpr int DM_DEPTH = 2;
-template <int G, bool ALLSAME>
+// VARLEN (with ALLSAME; spmm_decode_xattn): the keys / values of a wave are the kv_len[u] rows of ITS molecule's source in a packed, token-major
+// buffer -- a masked, variable-length memory (the encoded reactants of reaction prediction, SPMM_models_rxn.py).  The same loop: the number
+// of keys nv, hence the number of blocks, is per wave (still wave-uniform); keys >= nv are masked to -inf and never fetched (the DMA source is
+// clamped to key nv - 1, the source's last row), so no row of another source -- or past the buffer -- is read.
+template <int G, bool ALLSAME, bool VARLEN = false>
 __global__ __launch_bounds__(64) void decode_attn_mfma_kernel(DecAttnP p, int LD) {
+  static_assert(ALLSAME || !VARLEN, "a variable-length memory is shared by the beams of a molecule");
   constexpr int D = DM_DEPTH;
   extern __shared__ __attribute__((aligned(16))) char dm_smem[];
   const int lane = threadIdx.x;
@@ -145,7 +152,15 @@ __global__ __launch_bounds__(64) void decode_attn_mfma_kernel(DecAttnP p, int LD
   if (gw >= (long)nmol * p.nH) return;
   const int n = (int)(gw / p.nH), h = (int)(gw - (long)n * p.nH);
   const int r16 = lane & 15, q4 = lane >> 4;
-  const int Lkv = p.t_ptr ? min(*p.t_ptr + 1, p.Lkv) : p.Lkv;
+  int Lkv = p.t_ptr ? min(*p.t_ptr + 1, p.Lkv) : p.Lkv;
+  int row0 = 0;                                      // VARLEN: first row of the molecule's source
+  if constexpr (VARLEN) {
+    // three dependent loads the compiler counts; made scalars here, so they have landed -- and the block count below is provably
+    // wave-uniform -- before the first DMA.  The length is clamped into [1, Lkv]: a bad one cannot address outside Lkv rows of the source.
+    const int u = p.kv_seq ? p.kv_seq[n] : n;
+    row0 = __builtin_amdgcn_readfirstlane(p.kv_row0[u]);
+    Lkv = __builtin_amdgcn_readfirstlane(min(max(p.kv_len[u], 1), p.Lkv));
+  }
   const uint32_t ring0 = (uint32_t)(uintptr_t)(LDS_AS char*)dm_smem;
   int* sanc = (int*)(dm_smem + D * DM_SLOT);         // cache row of position j for each beam (not ALLSAME)
 
@@ -205,9 +220,11 @@ __global__ __launch_bounds__(64) void decode_attn_mfma_kernel(DecAttnP p, int LD
   // the compiler's own loads are complete before the first DMA is issued: its wait-count bookkeeping does not see the DMA below, and a
   // load it still believed pending would cost a full drain at its first use INSIDE the loop, on every trip
   asm volatile("" : "+v"(qf[0]), "+v"(qf[1])::"memory");
+  if constexpr (VARLEN) asm volatile("" : "+s"(row0), "+s"(Lkv)::"memory");
   const int nv = s + G * (Lkv - s);                 // virtual keys: s shared ones, then G per position
   const int nblk = (nv + 15) >> 4;
-  const int row_same = (n * G) / max(p.kv_div, 1);
+  // ALLSAME: element offset of key 0 of the rows every beam reads
+  const long base_same = VARLEN ? (long)row0 * p.tok_stride : (long)((n * G) / max(p.kv_div, 1)) * p.seq_stride;
   const long hbase = (long)h * p.head_stride;
   const int tok = (int)p.tok_stride;                // (Lkv <= 256 positions: j * tok_stride fits 32 bits for any cache this launcher accepts)
   // element offset of virtual key v's row of this head (keys past the end re-read the last one: masked where they are used, and a
@@ -215,7 +232,7 @@ __global__ __launch_bounds__(64) void decode_attn_mfma_kernel(DecAttnP p, int LD
   auto vk_ptr = [&](int v, bool shared, const bf16*& kp, const bf16*& vp) {
     long off;
     if (ALLSAME) {
-      off = (long)row_same * p.seq_stride + (long)(min(v, nv - 1) * tok) + hbase;
+      off = base_same + (long)(min(v, nv - 1) * tok) + hbase;
     } else if (shared) {                             // a block of keys every beam reads from beam 0's rows
       off = (long)sanc[v] * p.seq_stride + (long)(v * tok) + hbase;
     } else {
@@ -368,8 +385,22 @@ void launch_group(DecAttnP p, hipStream_t stream) {
   const int LD = p.anc ? (p.Lkv + 3) & ~3 : 0;
   const unsigned lds = (unsigned)DM_DEPTH * DM_SLOT + G * (unsigned)LD * 4u;    // ring + ancestry rows: <= 16 KiB
   const dim3 grid((unsigned)((waves + 7) / 8 * 8));
-  if (p.anc) hipLaunchKernelGGL((decode_attn_mfma_kernel<G, false>), grid, dim3(64), lds, stream, p, LD);
+  if (p.kv_len) hipLaunchKernelGGL((decode_attn_mfma_kernel<G, true, true>), grid, dim3(64), lds, stream, p, LD);
+  else if (p.anc) hipLaunchKernelGGL((decode_attn_mfma_kernel<G, false>), grid, dim3(64), lds, stream, p, LD);
   else hipLaunchKernelGGL((decode_attn_mfma_kernel<G, true>), grid, dim3(64), lds, stream, p, LD);
+}
+
+void launch_any_group(const DecAttnP& p, hipStream_t stream) {
+  switch (p.group) {
+    case 1: launch_group<1>(p, stream); break;
+    case 2: launch_group<2>(p, stream); break;
+    case 3: launch_group<3>(p, stream); break;
+    case 4: launch_group<4>(p, stream); break;
+    case 5: launch_group<5>(p, stream); break;
+    case 6: launch_group<6>(p, stream); break;
+    case 7: launch_group<7>(p, stream); break;
+    default: launch_group<8>(p, stream); break;
+  }
 }
 
 }  // namespace
@@ -389,27 +420,36 @@ extern "C" int spmm_decode_attn(const void* q, long ldq, const void* K, const vo
   const long waves = (long)R * nH;
   const int nblocks = (int)((waves + 3) / 4);
   DecAttnP p = {(const bf16*)q, ldq, (const bf16*)K, (const bf16*)V, seq_stride, tok_stride, head_stride, anc, anc_ld, kv_div, group, nblocks,
-                (bf16*)out, ldo, R, nH, Lkv, scale, t_ptr, rowmap, (const bf16*)knew, (const bf16*)vnew, ldn};
+                (bf16*)out, ldo, R, nH, Lkv, scale, t_ptr, rowmap, (const bf16*)knew, (const bf16*)vnew, ldn, nullptr, nullptr, nullptr};
   // beams of a molecule on one wave whenever the K/V rows of a group are (mostly) shared: cross-attention (kv_div == group) and
   // self-attention through an ancestry table
   static const bool per_beam = getenv("SPMM_DECODE_PER_BEAM") != nullptr;       // (debugging aid: the one-wave-per-row kernel)
   const bool grouped = !per_beam && group >= 1 && group <= 8 && (anc != nullptr || kv_div == group);
   if (grouped) {
-    switch (group) {
-      case 1: launch_group<1>(p, stream); break;
-      case 2: launch_group<2>(p, stream); break;
-      case 3: launch_group<3>(p, stream); break;
-      case 4: launch_group<4>(p, stream); break;
-      case 5: launch_group<5>(p, stream); break;
-      case 6: launch_group<6>(p, stream); break;
-      case 7: launch_group<7>(p, stream); break;
-      default: launch_group<8>(p, stream); break;
-    }
+    launch_any_group(p, stream);
   } else {
     if (knew) hipLaunchKernelGGL(cache_write_kernel, dim3((unsigned)(((long)R * nH * 8 + 255) / 256)), dim3(256), 0, stream, p, Lkv - 1);
     hipLaunchKernelGGL(decode_attn_kernel, dim3((unsigned)((nblocks + 7) / 8 * 8)), dim3(256), 0, stream, p);
   }
   SPMM_LAUNCH_CHECK("spmm_decode_attn");
+  return SPMM_OK;
+}
+
+extern "C" int spmm_decode_xattn(const void* q, long ldq, const void* K, const void* V, long ldkv, const int* kv_seq, const int* kv_row0,
+                                 const int* kv_len, int group, void* out, long ldo, int R, int nH, int Lkv_max, float scale, hipStream_t stream) {
+  SPMM_CHECK_SHAPE(q != nullptr && K != nullptr && V != nullptr && out != nullptr && kv_row0 != nullptr && kv_len != nullptr,
+                   "spmm_decode_xattn: q, K, V, out, kv_row0 and kv_len are required");
+  SPMM_CHECK_SHAPE(R > 0 && nH > 0 && Lkv_max >= 1 && Lkv_max <= 256, "spmm_decode_xattn: R=%d nH=%d Lkv_max=%d (1 <= Lkv_max <= 256)", R, nH, Lkv_max);
+  SPMM_CHECK_SHAPE(group >= 1 && group <= 8 && R % group == 0, "spmm_decode_xattn: R=%d must be a multiple of group=%d (1 <= group <= 8)", R, group);
+  SPMM_CHECK_SHAPE(ldkv >= (long)nH * 64 && ldkv % 8 == 0 && ldkv * 255 < (1L << 31), "spmm_decode_xattn: ldkv=%ld (a multiple of 8, >= nH*64, 255 * ldkv < 2^31)", ldkv);
+  SPMM_CHECK_SHAPE(ldq >= (long)nH * 64 && ldo >= (long)nH * 64 && ldq % 8 == 0 && ldo % 8 == 0,
+                   "spmm_decode_xattn: ldq=%ld ldo=%ld must keep 16-B alignment (multiples of 8, >= nH*64)", ldq, ldo);
+  SPMM_CHECK_SHAPE((((uintptr_t)q | (uintptr_t)K | (uintptr_t)V) & 15) == 0 && ((uintptr_t)out & 7) == 0,
+                   "spmm_decode_xattn: misaligned pointer (q, K, V: 16 bytes; out: 8)");
+  DecAttnP p = {(const bf16*)q, ldq, (const bf16*)K, (const bf16*)V, 0, ldkv, 64, nullptr, 0, group, group, 0,
+                (bf16*)out, ldo, R, nH, Lkv_max, scale, nullptr, nullptr, nullptr, nullptr, 0, kv_seq, kv_row0, kv_len};
+  launch_any_group(p, stream);
+  SPMM_LAUNCH_CHECK("spmm_decode_xattn");
   return SPMM_OK;
 }
 
@@ -429,6 +469,7 @@ struct BeamP {
   const int* mol;              // optional: state index (tokens, scores, finals, flags) of compact molecule i -- the live subset after a compaction
   const int* rowmap;           // optional: K/V cache row of compact beam row i*k + b (the "own row" written into the ancestry table)
   const float* noise; long ldn;   // SAMPLED instantiation: [N*k, >= V] fp32 added to the logits for the candidate selection only
+  int need;                       // finals that end a molecule's search: k (d_pv2smiles_batched.py) .. k*k (evaluate_beam, d_rxn_prediction.py)
 };
 constexpr int BEAM_KMAX = 8, BEAM_SEP = 3;
 
@@ -513,7 +554,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamP p) {
     for (int c = 0; c < kk2; ++c) {
       if (__shfl(my_tok, c, 64) != BEAM_SEP) continue;                  // wave-uniform
       const float lp = __shfl(my_lp, c, 64);
-      const int slot = fin_n < p.F ? fin_n : p.F;                       // slot F: write-only dump (never reached with F = 2k)
+      const int slot = fin_n < p.F ? fin_n : p.F;                       // slot F: write-only dump (never reached with F >= need + k - 1)
       const int* src = p.tokens + ((long)n * k + c / k) * L;
       int* dst = p.fin_tok + ((long)n * F1 + slot) * L;
       for (int pos = lane; pos < L; pos += 64) dst[pos] = pos == t ? BEAM_SEP : src[pos];
@@ -537,7 +578,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamP p) {
       if (lane == bi) cv = NEG;
     }
   }
-  const bool now_done = was_done || fin_n >= k;                         // a molecule that just reached k finals breaks before this update
+  const bool now_done = was_done || fin_n >= p.need;                    // a molecule that just reached its finals breaks before this update
   if (!now_done) {
     int tk[BEAM_KMAX][4], an[BEAM_KMAX][4];
 #pragma unroll
@@ -655,8 +696,19 @@ extern "C" int spmm_beam_step(const float* logits, long ldl, int N, int k, int V
                               int* anc, int anc_ld, int* ids_out, int* parent_out, int* n_done, const int* mol, const int* rowmap,
                               hipStream_t stream) {
   BeamP p = {logits, ldl, N, k, V, Lmax, F, t, t_ptr, t_off, tokens, cur_p, fin_p, fin_len, fin_tok, fin_n, done, anc, anc_ld, ids_out, parent_out, n_done, mol, rowmap,
-             nullptr, 0};
+             nullptr, 0, k};
   return beam_step_launch(p, stream, "spmm_beam_step");
+}
+
+extern "C" int spmm_beam_step_until(const float* logits, long ldl, int N, int k, int V, int Lmax, int F, int t, const int* t_ptr, int t_off,
+                                    int* tokens, float* cur_p, float* fin_p, int* fin_len, int* fin_tok, int* fin_n, unsigned char* done,
+                                    int* anc, int anc_ld, int* ids_out, int* parent_out, int* n_done, const int* mol, const int* rowmap,
+                                    int need, hipStream_t stream) {
+  BeamP p = {logits, ldl, N, k, V, Lmax, F, t, t_ptr, t_off, tokens, cur_p, fin_p, fin_len, fin_tok, fin_n, done, anc, anc_ld, ids_out, parent_out, n_done, mol, rowmap,
+             nullptr, 0, need};
+  SPMM_CHECK_SHAPE(k >= 1 && k <= BEAM_KMAX && need >= k && need <= k * k && F >= need + k - 1,
+                   "spmm_beam_step_until: k=%d (<= 8), need=%d outside [k, k*k], or F=%d < need + k - 1", k, need, F);
+  return beam_step_launch(p, stream, "spmm_beam_step_until");
 }
 
 extern "C" int spmm_beam_step_sampled(const float* logits, long ldl, int N, int k, int V, int Lmax, int F, int t, const int* t_ptr, int t_off,
@@ -665,7 +717,7 @@ extern "C" int spmm_beam_step_sampled(const float* logits, long ldl, int N, int 
                                       const float* noise, long ldn, hipStream_t stream) {
   SPMM_CHECK_SHAPE(noise != nullptr, "spmm_beam_step_sampled: noise is required (spmm_beam_step is the deterministic search)");
   BeamP p = {logits, ldl, N, k, V, Lmax, F, t, t_ptr, t_off, tokens, cur_p, fin_p, fin_len, fin_tok, fin_n, done, anc, anc_ld, ids_out, parent_out, n_done, mol, rowmap,
-             noise, ldn};
+             noise, ldn, k};
   return beam_step_launch(p, stream, "spmm_beam_step_sampled");
 }
 

@@ -135,11 +135,15 @@ class BeamBook:
     """The beam bookkeeping of the reference's search for N independent molecules at once, as tensor ops (no `.item()`):
     per molecule it makes exactly the decisions d_pv2smiles_batched.py:29-57 makes -- candidates ending in [SEP] are moved to
     `final` in row-major order and struck out with -1e5, the molecule stops once it holds >= k finals, the k best of the
-    k*k candidates survive."""
+    k*k candidates survive.  need (None: k): the number of finals that stops a molecule -- `evaluate_beam` of reaction prediction
+    (d_rxn_prediction.py:86-123) searches on until k*k hypotheses have ended; `results` returns the k best either way."""
 
-    def __init__(self, N: int, k: int, max_steps: int, device, fused: bool = False):
+    def __init__(self, N: int, k: int, max_steps: int, device, fused: bool = False, need: int | None = None):
         self.N, self.k, self.Lmax = N, k, max_steps + 3
-        self.F = 2 * k                                    # < k finals before the last appending step, <= k appended by it (one [SEP] per beam)
+        self.need = k if need is None else int(need)
+        if not k <= self.need <= k * k:
+            raise ValueError(f"need={need} outside [k, k*k] = [{k}, {k * k}]")
+        self.F = self.need + k                            # < need finals before the last appending step, <= k appended by it (one [SEP] per beam)
         it = torch.int32 if fused else torch.long         # fused: the state csrc/decode.hip::beam_step_kernel updates in place
         self.fused = fused
         self.tokens = torch.zeros(N, k, self.Lmax, dtype=it, device=device)
@@ -183,12 +187,12 @@ class BeamBook:
         new_p, flat = torch.topk(k2_p, k, dim=1)
         parent = flat // k
         tok = idx.gather(1, flat)
-        live = ~(self.done | (self.fin_n >= k))           # a molecule that just reached k finals breaks before this update
+        live = ~(self.done | (self.fin_n >= self.need))   # a molecule that just reached its finals breaks before this update
         new_tokens = self.tokens.gather(1, parent[:, :, None].expand(N, k, L))
         _set_column(new_tokens, t, tok)
         torch.where(live[:, None, None], new_tokens, self.tokens, out=self.tokens)
         torch.where(live[:, None], new_p, self.cur_p, out=self.cur_p)
-        self.done |= self.fin_n >= k
+        self.done |= self.fin_n >= self.need
         if host:
             self.t = t + 1
         return parent, tok
@@ -216,7 +220,7 @@ class BeamBook:
         return ids
 
     def all_done(self) -> bool:
-        """Host check (one small device read): every molecule holds its k finals."""
+        """Host check (one small device read): every molecule holds its finals."""
         return int(self.n_done.item()) == self.N if self.fused else bool(self.done.all())
 
     def results(self) -> List[List[Tuple[float, List[int]]]]:
@@ -273,16 +277,24 @@ class CachedDecoder:
     K/V projected once per molecule and shared by its k beams (cache slots sketched at
     xbert.py:291-295,480,1344-1348)."""
 
-    def __init__(self, model, prop_embeds: torch.Tensor, k: int, Lmax: int, repeat: int = 1, xkv: dict | None = None):
+    def __init__(self, model, prop_embeds: torch.Tensor | None, k: int, Lmax: int, repeat: int = 1, xkv: dict | None = None, memory: dict | None = None):
         """repeat: decode `repeat` molecules per row of prop_embeds (generation of many samples from one PV: the cross-attention keys /
-        values are projected once per row and copied).  xkv: the projections of an earlier decoder on the same prop_embeds (`xkv_once`)."""
+        values are projected once per row and copied).  xkv: the projections of an earlier decoder on the same prop_embeds (`xkv_once`).
+        memory (instead of prop_embeds): a masked, variable-length cross-attention memory, one source per molecule -- dict(N, xkv = {layer:
+        bf16 [M, 2H] keys | values of token-major rows}, row0 / len = int32 [N] first row and length of every source, Lmax = the longest
+        length allowed) -- read through spmm_decode_xattn; it is never moved: `compact` gathers the molecule -> source index alone."""
         from .engine import BF
         eng = model.engine
         self.eng, self.P, self.c, self.k = eng, eng.P, model.cfg.text, k
         self.pfx = "text_encoder."
         c, dev = self.c, model.device_
         self.device = dev
-        N, Lkv, H = prop_embeds.shape
+        self.mem, self.kv_seq = memory, None             # kv_seq: after compact(), the source of every molecule still decoded (None: its own)
+        if memory is not None:
+            assert prop_embeds is None and repeat == 1 and xkv is None
+            N, Lkv, H = memory["N"], memory["Lmax"], c.hidden_size
+        else:
+            N, Lkv, H = prop_embeds.shape
         N *= repeat
         assert Lmax <= 256 and H == c.hidden_size and c.hidden_size // c.num_attention_heads == 64
         self.N, self.R, self.Lmax, self.Lp, self.H = N, N * k, Lmax, Lkv, H
@@ -293,6 +305,9 @@ class CachedDecoder:
         self.rows = torch.arange(self.R, dtype=torch.int32, device=dev)
         self.cols = torch.arange(Lmax, device=dev)
         self.rowmap = None                               # after compact(): cache row of every beam row still decoded (None: the row itself)
+        if memory is not None:
+            self.xkv_once = self.xkv = memory["xkv"]
+            return
         if xkv is None:
             xkv = _cross_kv(eng, self.pfx + "bert.", c, prop_embeds.to(dev).to(BF).reshape(-1, H).contiguous())
         self.xkv_once = xkv                              # per row of prop_embeds
@@ -307,8 +322,12 @@ class CachedDecoder:
         cur = self.rows if self.rowmap is None else self.rowmap
         self.rowmap = cur.view(self.N, k)[keep].reshape(-1).contiguous()
         self.anc = self.anc.view(self.N, k, L)[keep].reshape(-1, L).contiguous()
-        for l, KV in self.xkv.items():
-            self.xkv[l] = KV.view(self.N, Lp, KV.shape[1])[keep].reshape(-1, KV.shape[1]).contiguous()
+        if self.mem is not None:                         # the memory stays where it is: only the molecule -> source index is gathered
+            cur = torch.arange(self.N, dtype=torch.int32, device=self.device) if self.kv_seq is None else self.kv_seq
+            self.kv_seq = cur[keep].contiguous()
+        else:
+            for l, KV in self.xkv.items():
+                self.xkv[l] = KV.view(self.N, Lp, KV.shape[1])[keep].reshape(-1, KV.shape[1]).contiguous()
         self.N = int(keep.numel())
         self.R = self.N * k
 
@@ -341,7 +360,11 @@ class CachedDecoder:
                 q = new(R, H)
                 ops.gemm_nt(a, P.wb(pf + "self.query.weight"), q, bias=P.w(pf + "self.query.bias"))
                 KV = self.xkv[l]
-                ops.decode_attn(q, KV[:, :H], KV[:, H:], ctx, nH=nH, Lkv=self.Lp, seq_stride=self.Lp * 2 * H, tok_stride=2 * H, kv_div=self.k, group=self.k)
+                if self.mem is None:
+                    ops.decode_attn(q, KV[:, :H], KV[:, H:], ctx, nH=nH, Lkv=self.Lp, seq_stride=self.Lp * 2 * H, tok_stride=2 * H, kv_div=self.k, group=self.k)
+                else:
+                    ops.decode_xattn(q, KV[:, :H], KV[:, H:], ctx, nH=nH, kv_seq=self.kv_seq, kv_row0=self.mem["row0"], kv_len=self.mem["len"],
+                                     Lkv_max=self.Lp, group=self.k)
                 a = sub(pf + "output.", ctx, a)[0]
             h = new(R, c.intermediate_size)
             ops.gemm_nt(a, P.wb(lp + "intermediate.dense.weight"), h, bias=P.w(lp + "intermediate.dense.bias"), epi=ops.EPI_GELU)
@@ -411,8 +434,9 @@ def _advance(dec, book: BeamBook, ids: torch.Tensor, t: int, *, t_dev: torch.Ten
 
 
 def _search(model, dec, N: int, *, k: int, max_steps: int, sync_every: int = 4, stochastic: bool = False, generator=None, graph: bool = False,
-            compact: bool = True, seed: int | None = None, mol_base: int = 0):
-    """beam_search_batched behind the decoder's construction (generate_with_property builds its decoders from one encoded PV)."""
+            compact: bool = True, seed: int | None = None, mol_base: int = 0, need: int | None = None):
+    """beam_search_batched behind the decoder's construction (generate_with_property builds its decoders from one encoded PV).
+    need: finals that end a molecule's search (BeamBook; None: k)."""
     last_run.clear()
     cached, dev = isinstance(dec, CachedDecoder), dec.device
     ids = torch.full((N * k,), CLS_ID, dtype=torch.long, device=dev)
@@ -422,7 +446,7 @@ def _search(model, dec, N: int, *, k: int, max_steps: int, sync_every: int = 4, 
     # one launch per position for the beam bookkeeping (csrc/decode.hip::beam_step_kernel: k <= 8 beams, vocabulary <= 512, histories <= 256
     # tokens -- the tensor-op bookkeeping serves everything else); spmm_gumbel_noise accepts the same shapes
     fits = bool(cached and k <= 8 and model.cfg.text.vocab_size <= 512 and Lmax <= 256)
-    book = BeamBook(N, k, max_steps, dev, fused=bool(fits and FUSED_BEAM_STEP and (seeded or not stochastic)))
+    book = BeamBook(N, k, max_steps, dev, fused=bool(fits and FUSED_BEAM_STEP and (seeded or not stochastic)), need=need)
     noise_at = _GumbelNoise(seed, mol_base, N, k, V, Lmax, dev, on_device=fits) if seeded else None
 
     def pick(logits, noise):
@@ -612,6 +636,157 @@ def predict_properties(model, text_ids: torch.Tensor, text_mask: torch.Tensor, n
     for i in range(n_props):
         dec.step(i)
     return dec.pred
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Reaction prediction (d_rxn_prediction.py, SPMM_models_rxn.py): the decoder cross-attends to the encoded reactant SMILES
+# ------------------------------------------------------------------------------------------------------------------
+RXN_MAX_STEPS = 100             # positions of `evaluate` / `evaluate_beam` (d_rxn_prediction.py:67,100)
+
+
+class RxnDecoder(CachedDecoder):
+    """The cached decoder of reaction prediction: the cross-attention memory of reaction n is its encoded reactant SMILES, 1 .. 256 tokens,
+    different for every reaction of the batch.  The reactants are encoded once by `text_encoder2` on packed rows (padding rows dropped, as
+    S2PDecoder encodes its text), the keys | values of every fusion layer are projected once from those rows, and the packed rows' start /
+    length tables are what spmm_decode_xattn reads them through.  text_mask: right-padded prefixes with at least one token each."""
+    EP = "text_encoder2.bert."
+
+    @torch.no_grad()
+    def __init__(self, model, text_ids: torch.Tensor, text_mask: torch.Tensor, k: int, Lmax: int):
+        from .engine import host_token_count
+        eng, ce, dev = model.engine, model.cfg_enc, model.device_
+        eng.train_mode = False
+        B, Lt = text_ids.shape
+        if not 1 <= k <= 8:
+            raise ValueError(f"{k} beams: spmm_decode_xattn serves 1..8 beams per reaction")
+        if Lt > ops.ATTN_MAXL:
+            raise ValueError(f"reactant sequences are limited to {ops.ATTN_MAXL} tokens (got {Lt}); the reference truncates at 150")
+        if Lt > ce.max_position_embeddings:
+            raise ValueError(f"sequence length {Lt} exceeds the {ce.max_position_embeddings} position embeddings")
+        host_mask = text_mask.detach().to("cpu")
+        n_tokens = host_token_count(host_mask)
+        if tuple(host_mask.shape) != (B, Lt) or n_tokens is None:
+            raise ValueError("text_mask must be [B, Lt] right-padded prefixes with at least one token per reaction")
+        ids32 = text_ids.to(dev).to(torch.int32).contiguous()
+        mask32 = host_mask.to(dev).to(torch.int32).contiguous()
+        x, _ = eng.embed_text(self.EP, ce, ids32, B, Lt, False)
+        pk = eng._pack_plan(mask32, B, Lt, n_tokens) if eng.pack_text else None
+        x, g, _ = eng.text_rows(x, mask32, pk)
+        text, _, _ = eng.stack_fwd(self.EP, ce, range(0, ce.fusion_layer), False, x, g, False)          # mode='text'
+        lens = host_mask.sum(1).to(torch.int32)
+        if pk:
+            row0, length = pk["row0"], pk["len"]
+        else:                                            # nothing to drop (or packing switched off): the dense [B, Lt] rows
+            row0, length = (torch.arange(B, dtype=torch.int32) * Lt).to(dev), lens.to(dev)
+        memory = dict(N=B, Lmax=Lt, xkv=_cross_kv(eng, "text_encoder.bert.", model.cfg.text, text), row0=row0.contiguous(), len=length.contiguous())
+        super().__init__(model, None, k, Lmax, memory=memory)
+        self.src_len = lens                              # host: tokens per reaction
+
+
+class _HostBeams:
+    """`evaluate_beam` (d_rxn_prediction.py:86-123) for one reaction through `model.generate`: whole-prefix forwards, host bookkeeping."""
+
+    def __init__(self, model, embeds, mask, k):
+        self.model, self.embeds, self.mask, self.k = model, embeds, mask, k
+
+    def top(self, prefix):
+        lp, ids = self.model.generate(self.embeds, self.mask, prefix, stochastic=False, k=self.k)
+        return lp.float(), ids
+
+    def run(self, max_steps):
+        k, dev = self.k, self.embeds.device
+        cls = torch.full((1, 1), CLS_ID, dtype=torch.long, device=dev)
+        lp, ids = self.top(cls)
+        beams = torch.cat([cls.expand(k, 1), ids.reshape(k, 1)], dim=1)
+        score = lp.reshape(k)
+        finals = []
+        for _ in range(max_steps):
+            lp, ids = self.top(beams)
+            cand_p = score[:, None] + lp
+            cand = torch.cat([beams[:, None, :].expand(k, k, beams.shape[1]), ids[:, :, None]], dim=2)
+            hits = (ids == SEP_ID).nonzero(as_tuple=False).tolist()                 # row-major
+            for b, j in hits:
+                finals.append((float(cand_p[b, j]), cand[b, j].tolist()))
+                cand_p[b, j] = -1e5
+            if hits and len(finals) >= k * k:
+                break
+            score, flat = torch.topk(cand_p.reshape(-1), k)
+            beams = cand.reshape(k * k, -1)[flat]
+        finals.sort(key=lambda h: h[0], reverse=True)                               # (stable)
+        return finals[:k]
+
+
+def _encode_reactants(model, text_ids, text_mask):
+    return model.text_encoder2.bert(text_ids, attention_mask=text_mask, return_dict=True, mode="text").last_hidden_state
+
+
+@torch.no_grad()
+def predict_products(model, text_ids: torch.Tensor, text_mask: torch.Tensor, k: int = 5, max_steps: int = RXN_MAX_STEPS, cached: bool | None = None,
+                     sync_every: int = 4, compact: bool = True) -> List[List[Tuple[float, List[int]]]]:
+    """`evaluate_beam` of d_rxn_prediction.py for a batch of reactions: text_ids / text_mask [N, Lt] are the reactant tokens as the encoder
+    sees them ([CLS] pieces [SEP] PAD.., the tokenizer's own first token dropped).  result[n]: up to k (log-prob, ids incl. [CLS] and [SEP]),
+    best first -- the k best of the k*k hypotheses the search collects before it stops (or of those that ended within max_steps positions).
+    cached=True (default on the HIP model): all reactions together on the engine (RxnDecoder, the one-launch beam step when it takes the
+    shape), finished reactions dropped as the search goes (`compact`).  cached=False: the reference's loop, one reaction at a time through
+    `model.text_encoder2.bert` and `model.generate` -- every position re-runs the whole prefix and re-projects the memory; it runs on any
+    object with that API."""
+    if cached is None:
+        cached = hasattr(model, "engine")
+    N = text_ids.shape[0]
+    if cached:
+        dec = RxnDecoder(model, text_ids, text_mask, k, max_steps + 3)
+        return _search(model, dec, N, k=k, max_steps=max_steps, sync_every=sync_every, compact=compact, need=k * k)
+    out = []
+    for n in range(N):
+        L = max(int(text_mask[n].sum()), 1)
+        ids, mask = text_ids[n:n + 1, :L], text_mask[n:n + 1, :L]
+        out.append(_HostBeams(model, _encode_reactants(model, ids, mask), mask, k).run(max_steps))
+    return out
+
+
+@torch.no_grad()
+def greedy_products(model, text_ids: torch.Tensor, text_mask: torch.Tensor, max_steps: int = RXN_MAX_STEPS, cached: bool | None = None,
+                    sync_every: int = 4) -> List[List[int]]:
+    """`evaluate` of d_rxn_prediction.py:56-81: the most probable next token of every reaction for up to max_steps positions, stopped once
+    every reaction has produced [SEP].  result[n]: the ids from [CLS] up to and including the first [SEP], or all max_steps + 1 of them when
+    there is none.  cached=True: one beam per reaction on the engine, ended flags on the device, one host read every `sync_every`
+    positions.  cached=False: the whole batch through `model.generate`, the prefix re-run at every position."""
+    if cached is None:
+        cached = hasattr(model, "engine")
+    N = text_ids.shape[0]
+    if cached:
+        dec = RxnDecoder(model, text_ids, text_mask, 1, max_steps + 3)
+        dev = dec.device
+        toks = torch.zeros(N, max_steps + 1, dtype=torch.long, device=dev)
+        toks[:, 0] = CLS_ID
+        ended = torch.zeros(N, dtype=torch.bool, device=dev)
+        ids = toks[:, 0].contiguous()
+        last_run.clear()
+        last_run.update(molecules=N, compactions=0, final_batch=N, positions=0)
+        for t in range(max_steps):
+            ids = torch.argmax(dec.step(ids, t), dim=-1)
+            toks[:, t + 1] = ids
+            ended |= ids == SEP_ID
+            last_run["positions"] = t + 1
+            if t % sync_every == sync_every - 1 and bool(ended.all()):
+                break
+        toks = toks.cpu()
+    else:
+        embeds = _encode_reactants(model, text_ids, text_mask)
+        toks = torch.full((N, 1), CLS_ID, dtype=torch.long, device=embeds.device)
+        ended = torch.zeros(N, 1, dtype=torch.bool, device=embeds.device)
+        for _ in range(max_steps):
+            nxt = model.generate(embeds, text_mask, toks, stochastic=False)
+            ended |= nxt == SEP_ID
+            toks = torch.cat([toks, nxt], dim=-1)
+            if bool(ended.all()):
+                break
+        toks = toks.cpu()
+    out = []
+    for row in toks.tolist():
+        row = row[:max_steps + 1]
+        out.append(row[:row.index(SEP_ID) + 1] if SEP_ID in row else row)
+    return out
 
 
 def _decode_graphed(dec: CachedDecoder, book: BeamBook, ids: torch.Tensor, max_steps: int, sync_every: int):

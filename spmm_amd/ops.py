@@ -491,10 +491,28 @@ def decode_attn(q, K, V, out, *, nH, Lkv, seq_stride, tok_stride, head_stride=64
     return out
 
 
-def beam_step(logits, book, *, t=0, t_ptr=None, t_off=0, anc=None, ids_out=None, parent_out=None, rowmap=None, noise=None):
+def decode_xattn(q, K, V, out, *, nH, kv_row0, kv_len, Lkv_max, kv_seq=None, group=1, scale=0.125):
+    """Single-query cross-attention over a masked, variable-length memory (csrc/decode.hip, spmm_decode_xattn): rows n*group .. of q / out
+    are the beams of molecule n, whose keys / values are rows kv_row0[u] .. + kv_len[u] - 1 of K / V (bf16 views of token-major rows with one
+    row stride: the halves of a fused key|value projection), u = kv_seq[n] (n when kv_seq is None).  kv_seq / kv_row0 / kv_len: int32 on the
+    device; Lkv_max <= 256 bounds every length."""
+    R = q.shape[0]
+    assert q.dtype == BF16 and K.dtype == BF16 and V.dtype == BF16 and out.dtype == BF16 and _row_stride(K) == _row_stride(V)
+    assert kv_row0.dtype == torch.int32 and kv_len.dtype == torch.int32 and kv_row0.numel() == kv_len.numel()
+    assert kv_row0.is_contiguous() and kv_len.is_contiguous()
+    assert kv_seq is None or (kv_seq.dtype == torch.int32 and kv_seq.is_contiguous() and kv_seq.numel() * group == R)
+    assert kv_seq is not None or kv_len.numel() * group >= R
+    _call("spmm_decode_xattn", _p(q), _row_stride(q), _p(K), _p(V), _row_stride(K), _p(kv_seq), _p(kv_row0), _p(kv_len), int(group), _p(out),
+          _row_stride(out), R, nH, int(Lkv_max), float(scale), _st())
+    return out
+
+
+def beam_step(logits, book, *, t=0, t_ptr=None, t_off=0, anc=None, ids_out=None, parent_out=None, rowmap=None, noise=None, need=None):
     """One position of the batched k-beam search on a decode.BeamBook with int32 state (csrc/decode.hip::beam_step_kernel): updates
     the book (and the ancestry table `anc` of the K/V cache) in place and returns the tokens to feed next, int32 [N*k].  noise (fp32
-    [N*k, V], e.g. from gumbel_noise): the sampled search -- candidates by logits + noise, log-probabilities of the logits themselves."""
+    [N*k, V], e.g. from gumbel_noise): the sampled search -- candidates by logits + noise, log-probabilities of the logits themselves.
+    A book with need != k (BeamBook(need=...)) ends a molecule's search at `need` finals instead of k (spmm_beam_step_until); `need` given
+    here overrides the book's."""
     _, k, L = book.tokens.shape
     mol = getattr(book, "mol", None)                      # int32 [N]: the live molecules of a compacted batch (None: all of them)
     N = book.tokens.shape[0] if mol is None else mol.numel()
@@ -508,7 +526,12 @@ def beam_step(logits, book, *, t=0, t_ptr=None, t_off=0, anc=None, ids_out=None,
     args = (_p(logits), logits.stride(0), N, k, logits.shape[1], L, book.F, int(t), _p(t_ptr), int(t_off), _p(book.tokens),
             _p(book.cur_p), _p(book.fin_p), _p(book.fin_len), _p(book.fin_tok), _p(book.fin_n), _p(book.done), _p(anc),
             0 if anc is None else anc.stride(0), _p(ids_out), _p(parent_out), _p(book.n_done), _p(mol), _p(rowmap))
-    if noise is None:
+    until = need is not None                             # (an explicit need, k included, goes through spmm_beam_step_until)
+    need = int(getattr(book, "need", k) if need is None else need)      # finals that end a molecule's search (k: the two original entry points)
+    if until or need != k:
+        assert noise is None, "the sampled search ends at k finals"
+        _call("spmm_beam_step_until", *args, need, _st())
+    elif noise is None:
         _call("spmm_beam_step", *args, _st())
     else:
         assert noise.dtype == torch.float32 and noise.dim() == 2 and noise.stride(1) == 1 and noise.device == logits.device
