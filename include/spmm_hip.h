@@ -253,6 +253,7 @@ int spmm_embed_ln_fwd(int mode, const int* ids, const float* word, const float* 
                       const float* pv_masktok, int src_mod, const float* gamma, const float* beta, void* y, void* zout,
                       float* mean, float* rstd, long nseq, int L, int H, float eps, float dropout_p,
                       const uint64_t* seed_ptr, uint64_t salt, spmm_stream_t stream);
+/* Backward of the embedding sum, modes 0 and 1 only (inputs_embeds takes no gradient here); every tensor of the mode is required. */
 int spmm_embed_bwd(int mode, const void* dz, const int* ids, const float* pv_x, const float* pv_mask, int src_mod,
                    float* dword, float* dpos, float* dtype0, float* d_w, float* d_b, float* d_cls, float* d_masktok,
                    long nseq, int L, int H, spmm_stream_t stream);

@@ -731,6 +731,7 @@ extern "C" int spmm_gemm_tn(const void* A, long lda, const void* B, long ldb, in
 extern "C" int spmm_gemm_tn_reduce(const float* ws, int ns, int N, int K, float* C, long ldc, spmm_stream_t stream) {
   SPMM_CHECK_SHAPE(ws != nullptr && C != nullptr && ns >= 1 && N > 0 && K > 0 && K % 4 == 0 && ldc % 4 == 0,
                    "spmm_gemm_tn_reduce: ns=%d N=%d K=%d ldc=%ld", ns, N, K, ldc);
+  SPMM_CHECK_SHAPE(ldc >= K, "spmm_gemm_tn_reduce: ldc=%ld is shorter than a row of K=%d", ldc, K);
   tn_reduce_launch(ws, ns, N, K, C, ldc, stream);
   SPMM_LAUNCH_CHECK("spmm_gemm_tn_reduce");
   return SPMM_OK;
@@ -738,6 +739,7 @@ extern "C" int spmm_gemm_tn_reduce(const float* ws, int ns, int N, int K, float*
 
 extern "C" int spmm_colsum_bf16(const void* x, long ld, int R, int C, float* out, const int* R_dev, spmm_stream_t stream) {
   SPMM_CHECK_SHAPE(R > 0 && C > 0 && ld % 8 == 0 && ((uintptr_t)x % 16 == 0), "spmm_colsum_bf16: R=%d C=%d ld=%ld (ld %% 8, 16-B aligned)", R, C, ld);
+  SPMM_CHECK_SHAPE(x != nullptr && out != nullptr && ld >= C, "spmm_colsum_bf16: null x / out, or ld=%ld shorter than a row of C=%d", ld, C);
   hipLaunchKernelGGL(colsum_kernel, dim3((C + 127) / 128, (R + CS_ROWS - 1) / CS_ROWS), dim3(256), 0, stream, (const bf16*)x, ld, R, C, out, R_dev);
   SPMM_LAUNCH_CHECK("spmm_colsum_bf16");
   return SPMM_OK;

@@ -254,6 +254,7 @@ int blocks_for(long work, int block) {
 
 extern "C" int spmm_gather_rows2(void* dst, const void* srcA, const void* srcB, const long* idx, long rows, int H, hipStream_t stream) {
   SPMM_CHECK_SHAPE(rows > 0 && H > 0 && H % 8 == 0 && idx && srcA, "spmm_gather_rows2: rows=%ld H=%d", rows, H);
+  SPMM_CHECK_SHAPE(dst != nullptr, "spmm_gather_rows2: null dst");
   hipLaunchKernelGGL(gather_rows2_kernel, dim3(blocks_for(rows * (H / 8), 256)), dim3(256), 0, stream, (bf16*)dst, (const bf16*)srcA,
                      (const bf16*)(srcB ? srcB : srcA), idx, rows, H);
   SPMM_LAUNCH_CHECK("spmm_gather_rows2");
@@ -262,12 +263,14 @@ extern "C" int spmm_gather_rows2(void* dst, const void* srcA, const void* srcB, 
 
 extern "C" int spmm_add_rows_bf16(void* dst, const long* idx, const void* src, long rows, int H, hipStream_t stream) {
   SPMM_CHECK_SHAPE(rows > 0 && H > 0 && H % 8 == 0 && idx, "spmm_add_rows_bf16: rows=%ld H=%d", rows, H);
+  SPMM_CHECK_SHAPE(dst && src, "spmm_add_rows_bf16: null dst / src");
   hipLaunchKernelGGL(add_rows_bf16_kernel, dim3(blocks_for(rows * (H / 8), 256)), dim3(256), 0, stream, (bf16*)dst, idx, (const bf16*)src, rows, H);
   SPMM_LAUNCH_CHECK("spmm_add_rows_bf16");
   return SPMM_OK;
 }
 
 extern "C" int spmm_zero_bytes(void* p, long nbytes, hipStream_t stream) {
+  SPMM_CHECK_SHAPE(p != nullptr, "spmm_zero_bytes: null p");
   SPMM_CHECK_SHAPE(nbytes > 0 && nbytes % 16 == 0 && ((uintptr_t)p & 15) == 0, "spmm_zero_bytes: %ld bytes at %p must be 16-byte granular", nbytes, p);
   hipLaunchKernelGGL(zero_bytes_kernel, dim3(blocks_for(nbytes / 16, 256)), dim3(256), 0, stream, (uint4*)p, nbytes / 16);
   SPMM_LAUNCH_CHECK("spmm_zero_bytes");
@@ -275,6 +278,8 @@ extern "C" int spmm_zero_bytes(void* p, long nbytes, hipStream_t stream) {
 }
 
 extern "C" int spmm_zero_rows(void* p, long rows, long row_bytes, long stride_bytes, hipStream_t stream) {
+  SPMM_CHECK_SHAPE(p != nullptr, "spmm_zero_rows: null p");
+  SPMM_CHECK_SHAPE(rows == 1 || stride_bytes >= row_bytes, "spmm_zero_rows: stride_bytes=%ld is shorter than a row of %ld bytes", stride_bytes, row_bytes);
   SPMM_CHECK_SHAPE(rows > 0 && row_bytes > 0 && row_bytes % 16 == 0 && stride_bytes % 16 == 0 && ((uintptr_t)p & 15) == 0,
                    "spmm_zero_rows: %ld rows of %ld bytes at stride %ld must be 16-byte granular", rows, row_bytes, stride_bytes);
   hipLaunchKernelGGL(zero_rows_kernel, dim3(blocks_for(rows * (row_bytes / 16), 256)), dim3(256), 0, stream, (char*)p, rows, row_bytes / 16, stride_bytes);
@@ -284,6 +289,7 @@ extern "C" int spmm_zero_rows(void* p, long rows, long row_bytes, long stride_by
 
 extern "C" int spmm_gelu_bwd(const void* dz, const void* pre, void* out, long n, hipStream_t stream) {
   SPMM_CHECK_SHAPE(n > 0 && n % 8 == 0, "spmm_gelu_bwd: n=%ld must be a positive multiple of 8", n);
+  SPMM_CHECK_SHAPE(dz && pre && out, "spmm_gelu_bwd: null dz / pre / out");
   hipLaunchKernelGGL(gelu_bwd_kernel, dim3(blocks_for(n / 8, 256)), dim3(256), 0, stream, (const bf16*)dz, (const bf16*)pre, (bf16*)out, n / 8);
   SPMM_LAUNCH_CHECK("spmm_gelu_bwd");
   return SPMM_OK;

@@ -507,8 +507,9 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(EmbedP p) {
 }
 
 // Backward of the embedding sum, given dz [nseq*L, H] (gradient w.r.t. the pre-LayerNorm sum, bf16).
-// One workgroup per position l; threads stride over H; loop over sequences.  dpos[l] has a single owner,
-// type0 / cls / masktok / w / b get one atomicAdd per column per workgroup, word rows are scattered with atomics
+// One workgroup per (position l, slice of the sequences): gridDim.y = 16 slices from 32 sequences on, else one; a slice past the last
+// sequence is empty and adds zeros.  Threads stride over H and loop over the slice's sequences.  dpos[l] / type0 / cls / masktok / w / b
+// get one atomicAdd per column per workgroup (dpos[l] has one owner only while gridDim.y == 1), word rows are scattered with atomics
 // (PAD id 0 skipped: nn.Embedding padding_idx, xbert.py:178).
 struct EmbedBwdP {
   const bf16* dz; const int* ids; const float* pv_x; const float* pv_mask; int src_mod;
@@ -692,6 +693,8 @@ extern "C" int spmm_ln_fwd(const void* x, const void* res, const float* gamma, c
                            const uint64_t* seed_ptr, uint64_t salt, const int* rows_dev, hipStream_t stream) {
   SPMM_CHECK_SHAPE(rows > 0 && H > 0 && H % 4 == 0 && H <= 1024, "spmm_ln_fwd: rows=%ld H=%d (need H%%4==0, H<=1024)", rows, H);
   SPMM_CHECK_SHAPE(dropout_p == 0.f || seed_ptr, "spmm_ln_fwd: dropout needs a device seed");
+  SPMM_CHECK_SHAPE(x && gamma && beta && y, "spmm_ln_fwd: null x / gamma / beta / y");
+  SPMM_CHECK_SHAPE((mean == nullptr) == (rstd == nullptr), "spmm_ln_fwd: mean and rstd come together");
   const uint32_t th = (uint32_t)(dropout_p * 65536.f + 0.5f);
   const float ds = 1.f / (1.f - dropout_p);
 #define LN_FWD16(NC)                                                                                                          \
@@ -729,6 +732,7 @@ extern "C" int spmm_ln_bwd(const void* dy, const void* dy2, const void* z, const
   SPMM_CHECK_SHAPE(beta_from_y != nullptr || mean != nullptr, "spmm_ln_bwd: the row means are required unless `z` holds the LayerNorm output (beta_from_y)");
   SPMM_CHECK_SHAPE(beta_from_y == nullptr || !drop_on_dy, "spmm_ln_bwd: the output of a LayerNorm followed by dropout does not determine the normalised values");
   SPMM_CHECK_SHAPE(dropout_p == 0.f || seed_ptr, "spmm_ln_bwd: dropout needs a device seed");
+  SPMM_CHECK_SHAPE(dy && z && rstd && gamma && dz, "spmm_ln_bwd: null dy / z / rstd / gamma / dz");
   long g = (rows + 3) / 4;
   // Grid: every workgroup ends with 3 H same-address atomics (d gamma, d beta, bias-gradient column sums), so fewer, longer workgroups win until the
   // rows per wave get too few to keep loads in flight: rows / 64 workgroups, between 256 and 512 (round 6, tools/bench_ln.py: 85 k rows 110 -> 100 us,
@@ -762,7 +766,10 @@ extern "C" int spmm_embed_ln_fwd(int mode, const int* ids, const float* word, co
                                  const float* pv_cls, const float* pv_masktok, int src_mod, const float* gamma,
                                  const float* beta, void* y, void* zout, float* mean, float* rstd, long nseq, int L, int H,
                                  float eps, float dropout_p, const uint64_t* seed_ptr, uint64_t salt, hipStream_t stream) {
-  SPMM_CHECK_SHAPE(nseq > 0 && L > 0 && H % 4 == 0 && H <= 1024, "spmm_embed_ln_fwd: nseq=%ld L=%d H=%d", nseq, L, H);
+  SPMM_CHECK_SHAPE(nseq > 0 && L > 0 && H > 0 && H % 4 == 0 && H <= 1024, "spmm_embed_ln_fwd: nseq=%ld L=%d H=%d (need 0 < H <= 1024, H%%4==0)", nseq, L, H);
+  SPMM_CHECK_SHAPE(mode >= 0 && mode <= 2, "spmm_embed_ln_fwd: unknown mode %d", mode);
+  SPMM_CHECK_SHAPE(pos && type0 && gamma && beta && y, "spmm_embed_ln_fwd: null pos / type0 / gamma / beta / y");
+  SPMM_CHECK_SHAPE((mean == nullptr) == (rstd == nullptr), "spmm_embed_ln_fwd: mean and rstd come together");
   SPMM_CHECK_SHAPE(mode == 0 ? (ids && word) : mode == 2 ? (pv_x != nullptr) : (pv_x && pv_mask && pv_w && pv_b && pv_cls && pv_masktok && src_mod > 0),
                    "spmm_embed_ln_fwd: missing inputs for mode %d", mode);
   SPMM_CHECK_SHAPE(dropout_p == 0.f || seed_ptr, "spmm_embed_ln_fwd: dropout needs a device seed");
@@ -793,6 +800,11 @@ extern "C" int spmm_embed_bwd(int mode, const void* dz, const int* ids, const fl
                               float* dword, float* dpos, float* dtype0, float* d_w, float* d_b, float* d_cls,
                               float* d_masktok, long nseq, int L, int H, hipStream_t stream) {
   SPMM_CHECK_SHAPE(nseq > 0 && L > 0 && H > 0, "spmm_embed_bwd: nseq=%ld L=%d H=%d", nseq, L, H);
+  SPMM_CHECK_SHAPE(mode == 0 || mode == 1, "spmm_embed_bwd: mode %d (0 = text, 1 = PV; inputs_embeds has no backward)", mode);
+  SPMM_CHECK_SHAPE(dz && dpos && dtype0, "spmm_embed_bwd: null dz / dpos / dtype0");
+  SPMM_CHECK_SHAPE(mode != 0 || (ids && dword), "spmm_embed_bwd: mode 0 needs ids and dword");
+  SPMM_CHECK_SHAPE(mode != 1 || (pv_x && pv_mask && d_w && d_b && d_cls && d_masktok), "spmm_embed_bwd: mode 1 needs pv_x, pv_mask, d_w, d_b, d_cls and d_masktok");
+  SPMM_CHECK_SHAPE(mode != 1 || src_mod > 0, "spmm_embed_bwd: mode 1 needs src_mod > 0, got src_mod=%d", src_mod);
   EmbedBwdP p = {(const bf16*)dz, ids, pv_x, pv_mask, src_mod, dword, dpos, dtype0, d_w, d_b, d_cls, d_masktok, nseq, L, H, mode};
   hipLaunchKernelGGL(embed_bwd_kernel, dim3(L, nseq >= 32 ? 16 : 1), dim3(256), 0, stream, p);
   SPMM_LAUNCH_CHECK("spmm_embed_bwd");
@@ -821,6 +833,7 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(const bf16* __restrict
 
 extern "C" int spmm_segment_sum_bf16(const void* src, const int* start, const int* list, void* out, int U, long W, hipStream_t stream) {
   SPMM_CHECK_SHAPE(U > 0 && U <= 65535 && W > 0 && W % 8 == 0, "spmm_segment_sum_bf16: U=%d W=%ld (W %% 8 == 0)", U, W);
+  SPMM_CHECK_SHAPE(src && start && list && out, "spmm_segment_sum_bf16: null src / start / list / out");
   hipLaunchKernelGGL(segment_sum_kernel, dim3((unsigned)((W / 8 + 255) / 256), U), dim3(256), 0, stream, (const bf16*)src, start, list,
                      (bf16*)out, W);
   SPMM_LAUNCH_CHECK("spmm_segment_sum_bf16");
@@ -830,6 +843,8 @@ extern "C" int spmm_segment_sum_bf16(const void* src, const int* start, const in
 extern "C" int spmm_transpose_bf16(const void* in, long ldi, void* out, long ldo, int R, int C, int Rpad, float* colsum,
                                    hipStream_t stream) {
   SPMM_CHECK_SHAPE(R > 0 && C > 0 && Rpad >= R && ldo >= Rpad, "spmm_transpose_bf16: R=%d C=%d Rpad=%d ldo=%ld", R, C, Rpad, ldo);
+  SPMM_CHECK_SHAPE(ldi >= C, "spmm_transpose_bf16: ldi=%ld is shorter than a row of C=%d", ldi, C);
+  SPMM_CHECK_SHAPE(in && out, "spmm_transpose_bf16: null in / out");
   hipLaunchKernelGGL(transpose_bf16_kernel, dim3((C + 63) / 64, (Rpad + 63) / 64), dim3(256), 0, stream, (const bf16*)in, ldi,
                      (bf16*)out, ldo, R, C, Rpad, colsum);
   SPMM_LAUNCH_CHECK("spmm_transpose_bf16");
@@ -838,6 +853,7 @@ extern "C" int spmm_transpose_bf16(const void* in, long ldi, void* out, long ldo
 
 extern "C" int spmm_cast_transpose(const float* in, void* out, void* outT, int R, int C, hipStream_t stream) {
   SPMM_CHECK_SHAPE(R > 0 && C > 0, "spmm_cast_transpose: R=%d C=%d", R, C);
+  SPMM_CHECK_SHAPE(in && (out || outT), "spmm_cast_transpose: null in, or neither out nor outT");
   hipLaunchKernelGGL(cast_transpose_kernel, dim3((C + 63) / 64, (R + 63) / 64), dim3(256), 0, stream, in, (bf16*)out, (bf16*)outT, R, C);
   SPMM_LAUNCH_CHECK("spmm_cast_transpose");
   return SPMM_OK;
@@ -853,12 +869,14 @@ extern "C" int spmm_cast_transpose_multi(const void* descs_dev, int ndesc, int t
 
 extern "C" int spmm_cast_f32_bf16(const float* in, void* out, long n, hipStream_t stream) {
   SPMM_CHECK_SHAPE(n > 0 && n % 4 == 0, "spmm_cast_f32_bf16: n=%ld must be a positive multiple of 4", n);
+  SPMM_CHECK_SHAPE(in && out, "spmm_cast_f32_bf16: null in / out");
   hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, stream, in, (bf16*)out, n / 4);
   SPMM_LAUNCH_CHECK("spmm_cast_f32_bf16");
   return SPMM_OK;
 }
 extern "C" int spmm_cast_bf16_f32(const void* in, float* out, long n, hipStream_t stream) {
   SPMM_CHECK_SHAPE(n > 0 && n % 4 == 0, "spmm_cast_bf16_f32: n=%ld must be a positive multiple of 4", n);
+  SPMM_CHECK_SHAPE(in && out, "spmm_cast_bf16_f32: null in / out");
   hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, stream, (const bf16*)in, out, n / 4);
   SPMM_LAUNCH_CHECK("spmm_cast_bf16_f32");
   return SPMM_OK;
@@ -867,6 +885,8 @@ extern "C" int spmm_cast_bf16_f32(const void* in, float* out, long n, hipStream_
 extern "C" int spmm_acc_rows(float* dst, long ldd, const void* src, long lds, const long* idx, long rows, int H, int atomic,
                              hipStream_t stream) {
   SPMM_CHECK_SHAPE(rows > 0 && H > 0 && H % 4 == 0, "spmm_acc_rows: rows=%ld H=%d", rows, H);
+  SPMM_CHECK_SHAPE(dst && src, "spmm_acc_rows: null dst / src");
+  SPMM_CHECK_SHAPE(rows == 1 || (ldd >= H && lds >= H), "spmm_acc_rows: ldd=%ld lds=%ld are shorter than a row of H=%d", ldd, lds, H);
   hipLaunchKernelGGL(acc_rows_kernel, dim3(grid_for(rows * (H / 4), 256)), dim3(256), 0, stream, dst, ldd, (const bf16*)src, lds,
                      idx, rows, H, atomic);
   SPMM_LAUNCH_CHECK("spmm_acc_rows");
@@ -874,6 +894,7 @@ extern "C" int spmm_acc_rows(float* dst, long ldd, const void* src, long lds, co
 }
 extern "C" int spmm_gather_rows(void* dst, const void* src, const long* idx, long rows, int H, hipStream_t stream) {
   SPMM_CHECK_SHAPE(rows > 0 && H > 0 && H % 8 == 0 && idx, "spmm_gather_rows: rows=%ld H=%d", rows, H);
+  SPMM_CHECK_SHAPE(dst && src, "spmm_gather_rows: null dst / src");
   hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(rows * (H / 8), 256)), dim3(256), 0, stream, (bf16*)dst, (const bf16*)src,
                      idx, rows, H);
   SPMM_LAUNCH_CHECK("spmm_gather_rows");

@@ -50,6 +50,89 @@ def test_bad_shape_is_reported_without_touching_the_gpu(built):
         L.call("spmm_enqueue", None, 5, 64, None, 16, None, None, 64, 4, None, 1, None, None)
 
 
+# Stands for "some non-null pointer" in calls that are refused before any launch (never dereferenced).  This file also runs where there
+# is a GPU: every call below must stay one that its entry point refuses BEFORE the launch -- never add a case here that is complete.
+P_ = 0x1000
+
+
+def _embed_fwd_args(mode=0, ids=P_, word=P_, pos=P_, type0=P_, pv_x=P_, pv_mask=P_, pv_w=P_, pv_b=P_, pv_cls=P_, pv_masktok=P_, src_mod=1,
+                    gamma=P_, beta=P_, y=P_, zout=None, mean=None, rstd=None, nseq=2, L=3, H=128):
+    return (mode, ids, word, pos, type0, pv_x, pv_mask, pv_w, pv_b, pv_cls, pv_masktok, src_mod, gamma, beta, y, zout, mean, rstd, nseq, L, H,
+            1e-12, 0.0, None, 0, None)
+
+
+def _embed_bwd_args(mode=0, dz=P_, ids=P_, pv_x=P_, pv_mask=P_, src_mod=1, dword=P_, dpos=P_, dtype0=P_, d_w=P_, d_b=P_, d_cls=P_, d_masktok=P_):
+    return (mode, dz, ids, pv_x, pv_mask, src_mod, dword, dpos, dtype0, d_w, d_b, d_cls, d_masktok, 2, 3, 128, None)
+
+
+def _ln_fwd_args(x=P_, gamma=P_, beta=P_, y=P_, mean=None, rstd=None):
+    return (x, None, gamma, beta, y, None, mean, rstd, 4, 128, 1e-12, 0.0, None, 0, None, None)
+
+
+# every call is complete except for the one thing named: (entry point, arguments, what the message must say)
+REFUSED = (
+    [("spmm_embed_bwd", _embed_bwd_args(0, **{k: None}), "mode 0 needs ids and dword") for k in ("ids", "dword")]
+    + [("spmm_embed_bwd", _embed_bwd_args(1, **{k: None}), "mode 1 needs pv_x, pv_mask") for k in ("pv_x", "pv_mask", "d_w", "d_b", "d_cls", "d_masktok")]
+    + [("spmm_embed_bwd", _embed_bwd_args(1, src_mod=sm), r"src_mod=-?\d") for sm in (0, -3)]
+    + [("spmm_embed_bwd", _embed_bwd_args(md), rf"spmm_embed_bwd: mode {md} ") for md in (2, -1, 3)]
+    + [("spmm_embed_bwd", _embed_bwd_args(md, **{k: None}), "spmm_embed_bwd: null dz / dpos / dtype0") for md in (0, 1) for k in ("dz", "dpos", "dtype0")]
+    + [("spmm_embed_ln_fwd", _embed_fwd_args(md, H=0), "spmm_embed_ln_fwd: nseq=2 L=3 H=0") for md in (0, 1, 2)]
+    + [("spmm_embed_ln_fwd", _embed_fwd_args(md, **{k: None}), "spmm_embed_ln_fwd: null pos / type0 / gamma / beta / y")
+       for md in (0, 2) for k in ("pos", "type0", "gamma", "beta", "y")]
+    + [("spmm_embed_ln_fwd", _embed_fwd_args(0, mean=P_), "spmm_embed_ln_fwd: mean and rstd come together"),
+       ("spmm_embed_ln_fwd", _embed_fwd_args(1, rstd=P_), "spmm_embed_ln_fwd: mean and rstd come together"),
+       ("spmm_embed_ln_fwd", _embed_fwd_args(3), "spmm_embed_ln_fwd: unknown mode 3"),
+       ("spmm_embed_ln_fwd", _embed_fwd_args(0, word=None), "missing inputs for mode 0"),
+       ("spmm_embed_ln_fwd", _embed_fwd_args(1, pv_cls=None), "missing inputs for mode 1"),
+       ("spmm_embed_ln_fwd", _embed_fwd_args(1, src_mod=0), "missing inputs for mode 1"),
+       ("spmm_embed_ln_fwd", _embed_fwd_args(2, pv_x=None), "missing inputs for mode 2"),
+       ("spmm_ln_fwd", _ln_fwd_args(mean=P_), "spmm_ln_fwd: mean and rstd come together"),
+       ("spmm_ln_fwd", _ln_fwd_args(rstd=P_), "spmm_ln_fwd: mean and rstd come together")]
+    + [("spmm_ln_fwd", _ln_fwd_args(**{k: None}), "spmm_ln_fwd: null x / gamma / beta / y") for k in ("x", "gamma", "beta", "y")]
+    + [("spmm_ln_bwd", tuple(None if i == k else a for i, a in enumerate((P_, None, P_, P_, P_, P_, P_, None, None, None, 4, 128, 0.0, None, 0, 0, None, None,
+                                                                          None, None))), "spmm_ln_bwd: null dy / z / rstd / gamma / dz")
+       for k in (0, 2, 4, 5, 6)]
+    + [("spmm_transpose_bf16", (P_, 39, P_, 64, 60, 40, 64, None, None), "spmm_transpose_bf16: ldi=39 is shorter than a row of C=40"),
+       ("spmm_transpose_bf16", (None, 40, P_, 64, 60, 40, 64, None, None), "spmm_transpose_bf16: null in / out"),
+       ("spmm_transpose_bf16", (P_, 40, None, 64, 60, 40, 64, None, None), "spmm_transpose_bf16: null in / out"),
+       ("spmm_segment_sum_bf16", (None, P_, P_, P_, 3, 64, None), "spmm_segment_sum_bf16: null src / start / list / out"),
+       ("spmm_segment_sum_bf16", (P_, None, P_, P_, 3, 64, None), "spmm_segment_sum_bf16: null src / start / list / out"),
+       ("spmm_segment_sum_bf16", (P_, P_, None, P_, 3, 64, None), "spmm_segment_sum_bf16: null src / start / list / out"),
+       ("spmm_segment_sum_bf16", (P_, P_, P_, None, 3, 64, None), "spmm_segment_sum_bf16: null src / start / list / out"),
+       ("spmm_acc_rows", (None, 128, P_, 128, None, 5, 128, 0, None), "spmm_acc_rows: null dst / src"),
+       ("spmm_acc_rows", (P_, 128, None, 128, None, 5, 128, 1, None), "spmm_acc_rows: null dst / src"),
+       ("spmm_acc_rows", (P_, 64, P_, 128, None, 5, 128, 0, None), "spmm_acc_rows: ldd=64 lds=128 are shorter"),
+       ("spmm_cast_transpose", (None, P_, P_, 4, 5, None), "spmm_cast_transpose: null in, or neither out nor outT"),
+       ("spmm_cast_transpose", (P_, None, None, 4, 5, None), "spmm_cast_transpose: null in, or neither out nor outT"),
+       ("spmm_cast_f32_bf16", (None, P_, 8, None), "spmm_cast_f32_bf16: null in / out"),
+       ("spmm_cast_bf16_f32", (P_, None, 8, None), "spmm_cast_bf16_f32: null in / out"),
+       ("spmm_gather_rows", (None, P_, P_, 3, 8, None), "spmm_gather_rows: null dst / src"),
+       ("spmm_gather_rows2", (None, P_, None, P_, 3, 8, None), "spmm_gather_rows2: null dst"),
+       ("spmm_add_rows_bf16", (P_, P_, None, 3, 8, None), "spmm_add_rows_bf16: null dst / src"),
+       ("spmm_gelu_bwd", (P_, None, P_, 8, None), "spmm_gelu_bwd: null dz / pre / out"),
+       ("spmm_zero_bytes", (None, 64, None), "spmm_zero_bytes: null p"),
+       ("spmm_zero_rows", (None, 3, 16, 48, None), "spmm_zero_rows: null p"),
+       ("spmm_zero_rows", (P_, 3, 32, 16, None), "spmm_zero_rows: stride_bytes=16 is shorter than a row of 32 bytes"),
+       ("spmm_colsum_bf16", (None, 8, 4, 8, P_, None, None), "spmm_colsum_bf16: null x / out"),
+       ("spmm_colsum_bf16", (P_, 8, 4, 8, None, None, None), "spmm_colsum_bf16: null x / out"),
+       ("spmm_colsum_bf16", (P_, 8, 4, 12, P_, None, None), "ld=8 shorter than a row of C=12"),
+       ("spmm_gemm_tn_reduce", (None, 1, 4, 4, P_, 4, None), "spmm_gemm_tn_reduce: ns=1 N=4 K=4 ldc=4"),
+       ("spmm_gemm_tn_reduce", (P_, 1, 4, 8, P_, 4, None), "spmm_gemm_tn_reduce: ldc=4 is shorter than a row of K=8")])
+
+
+@pytest.mark.parametrize("i", range(len(REFUSED)), ids=[f"{i}-{r[0]}" for i, r in enumerate(REFUSED)])
+def test_row_kernel_entry_points_refuse_incomplete_calls(built, i):
+    """The embedding, LayerNorm-forward, layout and row-helper entry points refuse a call with a missing tensor, an unknown mode or a stride
+    shorter than a row as a SHAPE error (rc = 1) that names the entry point and the argument -- before any launch, so this runs anywhere.
+    "launch failed" (rc = 2) on a machine without a GPU would mean the call got as far as the launch: a null dereference on a GPU."""
+    from spmm_amd._lib import lib
+    name, args, msg = REFUSED[i]
+    with pytest.raises(RuntimeError, match=msg) as e:
+        lib().call(name, *args)
+    assert f"{name} failed (rc=1)" in str(e.value) and "launch failed" not in str(e.value), str(e.value)
+    assert name in str(e.value).split("): ", 1)[1], "the message names its entry point: " + str(e.value)
+
+
 def test_product_refuses_to_run_without_the_extension(tmp_path):
     """No CPU / eager fallback: with the shared library missing the library handle and the ops that reach it raise and name the file
     they looked for (ops that take a stream fail even earlier on a box without a GPU: torch reports the missing device)."""
