@@ -319,6 +319,16 @@ int spmm_sample_neg(const float* S, long ldj, int B, const long* forced, const u
 int spmm_lm_loss(const float* logits, const float* logits_m, long ldl, const int* ids, long nseq, int L, int V,
                  const float* alpha_ptr, int* n_nonpad_ws, const float* gscale, void* dlogits, long ldd, int Vpad,
                  float* losses, int loss_slot, spmm_stream_t stream);
+/* seq2seq loss of the reaction model, CrossEntropyLoss(ignore_index=0) on the shifted product SPMM_models_rxn.py:31-46, on the decoder's
+ * rows as the engine holds them: logits fp32 [rows, ldl] (V real columns); ids int32 [nseq*L], the dense product; row_of [rows] = dense row
+ * of every packed row (the pack plan's `rows`; null: the rows are dense).  Row r with d = row_of ? row_of[r] : r predicts ids[d + 1] unless
+ * d % L == L - 1; a label of 0 or outside [0, V) is ignored and never indexes memory.  loss = mean over the n labelled rows, n counted on
+ * the device by the launch itself; n = 0 gives loss 0 and dlogits 0 (the reference divides 0 by 0).  dlogits (bf16 [rows, ldd], optional):
+ * gscale / n * (softmax - onehot) on labelled rows, zero elsewhere and in columns V..Vpad-1; every element is written.  n_label_ws: 4 ints,
+ * 8-byte aligned, as for spmm_lm_loss. */
+int spmm_s2s_loss(const float* logits, long ldl, const int* ids, const long* row_of, long rows, long nseq, int L, int V,
+                  int* n_label_ws, const float* gscale, void* dlogits, long ldd, int Vpad, float* losses, int loss_slot,
+                  spmm_stream_t stream);
 /* itm_head + cross entropy SPMM_models.py:201-206 (forward and backward in one pass). */
 int spmm_itm_head(const void* xa, long stride_a, const void* xb, long stride_b, int H, const float* W, const float* bias,
                   int n, int B, const float* gscale, float* losses, int loss_slot, float* logits_out, void* dxa, void* dxb,

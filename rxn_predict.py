@@ -12,7 +12,7 @@ source is always the first column.  What differs from the reference, on purpose:
 (and written back in input order), and every batch is decoded together on the engine (spmm_amd.decode.predict_products /
 greedy_products: reactants encoded once on packed rows, K/V cache, masked-memory cross-attention) -- the reference's beam search takes
 one reaction at a time.  Accuracy is the share of exact string matches; the strings are RDKit-canonical only if `rdkit` can be imported.
-Fine-tuning is not built."""
+Fine-tuning is rxn_finetune.py; with --synthetic an explicitly named --checkpoint (e.g. one rxn_finetune.py --synthetic wrote) replaces the seeded weights."""
 import argparse
 import csv
 import os
@@ -29,6 +29,7 @@ from smiles2pv import encode, length_sorted_batches, pad_batch      # noqa: E402
 
 MAX_SOURCE = 150          # d_rxn_prediction.py:63,92 (tokenizer(text, padding='longest', max_length=150))
 MAX_STEPS = 100           # positions of evaluate / evaluate_beam (:67, :100)
+DEFAULT_CHECKPOINT = "./output/RXN/checkpoint_best.pth"
 
 
 # --------------------------------------------------------------------------------------------------------------------- input
@@ -138,12 +139,12 @@ def main(args):
     model = SPMMRxn(config=config, device=device)
     if tokenizer is None:
         tokenizer = SmilesWordPiece(synthetic_vocab(model.cfg.text.vocab_size))
+    if args.checkpoint and (not args.synthetic or args.checkpoint != DEFAULT_CHECKPOINT):      # (--synthetic: seeded weights unless one is named)
+        res = model.load_pretrained(args.checkpoint)
+        print(f"load checkpoint from {args.checkpoint} (missing {len(res.missing_keys)}, unexpected {len(res.unexpected_keys)})")
     if args.synthetic:
         sources, targets = synthetic_reactions(tokenizer.itos, 8, args.seed)
     else:
-        if args.checkpoint:
-            res = model.load_pretrained(args.checkpoint)
-            print(f"load checkpoint from {args.checkpoint} (missing {len(res.missing_keys)}, unexpected {len(res.unexpected_keys)})")
         sources, targets = read_reactions(args.input)
     model.eval()
     print("=" * 50)
@@ -163,7 +164,7 @@ def main(args):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Predict the products (or reactants) of every reaction of a file (the reference's d_rxn_prediction.py --evaluate True).")
     # the reference's flags (d_rxn_prediction.py:259-268)
-    p.add_argument("--checkpoint", default="./output/RXN/checkpoint_best.pth")
+    p.add_argument("--checkpoint", default=DEFAULT_CHECKPOINT)
     p.add_argument("--mode", default="forward", choices=("forward", "retro"))
     p.add_argument("--n_beam", default=5, type=int, help="beams per reaction; 1 runs the greedy search")
     p.add_argument("--device", default="cuda")

@@ -285,6 +285,71 @@ __global__ __launch_bounds__(256) void lm_loss_kernel(const float* __restrict__ 
   if (threadIdx.x == 0) loss_partial_add((sh[0] + sh[1]) + (sh[2] + sh[3]), n_nonpad, losses + loss_slot);
 }
 
+// ---------------------------------------------------------------- seq2seq loss (one wave per decoder row)
+// CrossEntropyLoss(ignore_index=0) on the shifted product, SPMM_models_rxn.py:31-46, on the decoder's rows as the engine holds them:
+// row r is dense row d = row_of ? row_of[r] : r of the [nseq, L] product; its label is ids[d + 1] unless d is a last position.  A label
+// of 0 (PAD) is ignored, and so is one outside [0, V): it never indexes the row.  -> the label, 0 for a row without one.
+__device__ __forceinline__ int s2s_label(const int* __restrict__ ids, const long* __restrict__ row_of, long r, long nd, int L, int V) {
+  const long d = row_of ? row_of[r] : r;
+  if (d < 0 || d >= nd || (int)(d % L) == L - 1) return 0;
+  const int label = ids[d + 1];
+  return (label > 0 && label < V) ? label : 0;
+}
+__global__ __launch_bounds__(1024) void count_s2s_kernel(const int* __restrict__ ids, const long* __restrict__ row_of, long rows, long nd,
+                                                         int L, int V, int* __restrict__ out) {
+  __shared__ int sh[16];                               // one workgroup of 16 waves (the count is needed before s2s_loss starts)
+  int c = 0;
+  for (long r = threadIdx.x; r < rows; r += 1024) c += s2s_label(ids, row_of, r, nd, L, V) != 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = 0;
+    for (int w = 0; w < 16; ++w) t += sh[w];
+    *out = t;
+    out[1] = out[2] = out[3] = 0;                      // ticket and fixed-point sum of loss_partial_add
+  }
+}
+// loss = (1/n) sum over the n labelled rows of (lse - x[label]); dlogits = gscale / n * (softmax - onehot) on those rows, zero on every
+// other row and on the columns V..Vpad-1 (every element is written).  n = 0 (nothing but PAD targets): loss 0 and dlogits 0, where the
+// reference divides 0 by 0.  Shaped like lm_loss_kernel: workgroups stride over the rows and add one loss partial each.
+__global__ __launch_bounds__(256) void s2s_loss_kernel(const float* __restrict__ logits, long ldl, const int* __restrict__ ids,
+                                const long* __restrict__ row_of, long rows, long nd, int L, int V, int* __restrict__ ws,
+                                const float* __restrict__ gscale, bf16* __restrict__ dlogits, long ldd, int Vpad,
+                                float* __restrict__ losses, int loss_slot) {
+  __shared__ float sh[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = *ws;
+  const float inv_n = n > 0 ? 1.f / (float)n : 0.f;
+  const float g = (gscale ? *gscale : 1.f) * inv_n;
+  float lacc = 0.f;
+  for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
+    bf16* d = dlogits ? dlogits + row * ldd : nullptr;
+    const int label = s2s_label(ids, row_of, row, nd, L, V);
+    if (label == 0) {
+      if (d) for (int j = lane; j < Vpad; j += 64) d[j] = (bf16)0.f;
+      continue;
+    }
+    const float* x = logits + row * ldl;
+    float mx = -INFINITY;
+    for (int j = lane; j < V; j += 64) mx = fmaxf(mx, x[j]);
+    mx = wave_max(mx);
+    float se = 0.f;
+    for (int j = lane; j < V; j += 64) se += __expf(x[j] - mx);
+    se = wave_sum(se);
+    lacc += mx + __logf(se) - x[label];                                  // (wave-uniform)
+    if (d) {
+      const float inv_se = 1.f / se;
+      for (int j = lane; j < Vpad; j += 64)
+        d[j] = (bf16)(j < V ? g * (__expf(x[j] - mx) * inv_se - (j == label ? 1.f : 0.f)) : 0.f);
+    }
+  }
+  if (lane == 0) sh[wave] = lacc;
+  __syncthreads();
+  if (threadIdx.x == 0) loss_partial_add(((sh[0] + sh[1]) + (sh[2] + sh[3])) * inv_n, ws, losses + loss_slot);
+}
+
 // ---------------------------------------------------------------- ITM head fwd+bwd (one wave per pair row)
 // vl[i] = [xa[rowa(i)] | xb[rowb(i)]] (bf16 rows of width H), logits = vl W^T + b (W [2, 2H] fp32), CE vs label
 // (1 for i < B else 0), mean over n = 3B rows.  Writes d xa / d xb rows (bf16) and accumulates dW, db.
@@ -514,6 +579,20 @@ extern "C" int spmm_lm_loss(const float* logits, const float* logits_m, long ldl
   hipLaunchKernelGGL(lm_loss_kernel, dim3((nseq * L + 3) / 4 < 1024 ? (nseq * L + 3) / 4 : 1024), dim3(256), 0, stream, logits, logits_m, ldl, ids, nseq, L, V, alpha_ptr,
                      n_nonpad_ws, gscale, (bf16*)dlogits, ldd, Vpad, losses, loss_slot);
   SPMM_LAUNCH_CHECK("spmm_lm_loss");
+  return SPMM_OK;
+}
+extern "C" int spmm_s2s_loss(const float* logits, long ldl, const int* ids, const long* row_of, long rows, long nseq, int L, int V,
+                             int* n_label_ws, const float* gscale, void* dlogits, long ldd, int Vpad, float* losses, int loss_slot,
+                             hipStream_t stream) {
+  SPMM_CHECK_SHAPE(nseq > 0 && L > 1 && rows > 0 && rows <= nseq * L, "spmm_s2s_loss: rows=%ld nseq=%ld L=%d (L >= 2, 1 <= rows <= nseq*L)",
+                   rows, nseq, L);
+  SPMM_CHECK_SHAPE(V > 0 && Vpad >= V && ldl >= V && (!dlogits || ldd >= Vpad), "spmm_s2s_loss: V=%d Vpad=%d ldl=%ld ldd=%ld", V, Vpad, ldl, ldd);
+  SPMM_CHECK_SHAPE(logits && ids && losses, "spmm_s2s_loss: logits, ids and losses are required");
+  SPMM_CHECK_SHAPE(n_label_ws && (uintptr_t)n_label_ws % 8 == 0, "spmm_s2s_loss: the workspace is 4 ints, 8-byte aligned");
+  hipLaunchKernelGGL(count_s2s_kernel, dim3(1), dim3(1024), 0, stream, ids, row_of, rows, nseq * L, L, V, n_label_ws);
+  hipLaunchKernelGGL(s2s_loss_kernel, dim3((rows + 3) / 4 < 1024 ? (rows + 3) / 4 : 1024), dim3(256), 0, stream, logits, ldl, ids, row_of, rows,
+                     nseq * L, L, V, n_label_ws, gscale, (bf16*)dlogits, ldd, Vpad, losses, loss_slot);
+  SPMM_LAUNCH_CHECK("spmm_s2s_loss");
   return SPMM_OK;
 }
 extern "C" int spmm_itm_head(const void* xa, long stride_a, const void* xb, long stride_b, int H, const float* W, const float* bias,

@@ -49,10 +49,14 @@ class _CosineSchedule:
 
 class _FusedAdamW:
     """AdamW(lr, weight_decay on all params, betas (0.9,0.999), eps 1e-8) SPMM_models.py:340 + clip_grad_norm_(5.) :361
-    as three launches over the flat arena; exposes `param_groups[0]['lr']` like a torch optimizer."""
+    as three launches over the flat arena; exposes `param_groups[0]['lr']` like a torch optimizer.  `numel`: step only the first `numel`
+    elements of the arena -- what lies behind them (parameters no loss reaches, laid out last: spmm_amd/rxn.py) keeps its values, weight
+    decay included, and its Adam moments stay zero, as under a torch optimiser that skips parameters without a gradient."""
 
-    def __init__(self, store: ParamStore, eng: PretrainStep, lr: float, weight_decay: float, max_norm: float = 5.0):
+    def __init__(self, store: ParamStore, eng: PretrainStep, lr: float, weight_decay: float, max_norm: float = 5.0, numel: Optional[int] = None):
         self.store, self.eng, self.max_norm = store, eng, max_norm           # (max_norm = inf: no clipping, the fine-tuning scripts)
+        self.numel = store.total if numel is None else int(numel)
+        assert 0 < self.numel <= store.total
         self.param_groups = [{"lr": lr, "weight_decay": weight_decay, "betas": (0.9, 0.999), "eps": 1e-8}]
         dev = store.device
         self.normsq = torch.zeros(1, device=dev)
@@ -70,8 +74,11 @@ class _FusedAdamW:
         if fill_lr:                                  # (a host value: set outside a captured graph, see SPMM.fused_step_graphed)
             self.eng.lr.fill_(g["lr"])
         self.normsq.zero_()
-        ops.grad_sqnorm(self.store.grad, self.normsq)
-        ops.adamw_step(self.store.flat, self.store.grad, self.store.adam_m, self.store.adam_v, self.store.shadow, lr=self.eng.lr,
+        st = self.store
+        arenas = (st.flat, st.grad, st.adam_m, st.adam_v, st.shadow)
+        p, gr, am, av, sh = arenas if self.numel == st.total else (a[:self.numel] for a in arenas)
+        ops.grad_sqnorm(gr, self.normsq)
+        ops.adamw_step(p, gr, am, av, sh, lr=self.eng.lr,
                        beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"], normsq=self.normsq,
                        max_norm=self.max_norm, step=self.step_count, nan_flag=self.eng.nan_flag, scalars=self.scalars)
         # the transposed weight shadows are operands of the NEXT backward's data-gradient GEMMs only

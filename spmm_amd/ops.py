@@ -358,6 +358,20 @@ def lm_loss(logits, logits_m, ids, *, nseq, L, V, alpha, ws, losses, slot, dlogi
                V if dlogits is None else dlogits.shape[1], _p(losses), slot, _st())
 
 
+def s2s_loss(logits, ids, *, nseq, L, V, ws, losses, slot, row_of=None, dlogits=None, gscale=None):
+    """Next-token cross-entropy with label 0 ignored (csrc/losses.hip::s2s_loss_kernel) on the decoder's rows: logits fp32 [rows, >= V],
+    ids int32 [nseq*L] (the dense product), row_of int64 [rows] = dense row of every packed row (a pack plan's `rows`; None: dense rows).
+    dlogits (bf16 [rows, Vpad], uninitialised): every element is written."""
+    rows = logits.shape[0]
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] >= V and ids.dtype == torch.int32 and ids.numel() == nseq * L
+    assert ids.is_contiguous() and ws.dtype == torch.int32 and ws.numel() >= 4 and losses.dtype == torch.float32
+    assert row_of is None or (row_of.dtype == torch.int64 and row_of.numel() >= rows and row_of.is_contiguous())
+    assert row_of is not None or rows == nseq * L
+    assert dlogits is None or (dlogits.dtype == BF16 and dlogits.dim() == 2 and dlogits.shape[0] == rows)
+    _call("spmm_s2s_loss", _p(logits), _row_stride(logits), _p(ids), _p(row_of), rows, nseq, L, V, _p(ws), _p(gscale), _p(dlogits),
+          0 if dlogits is None else _row_stride(dlogits), V if dlogits is None else dlogits.shape[1], _p(losses), slot, _st())
+
+
 def itm_head(xa, stride_a, xb, stride_b, H, W, bias, *, n, B, losses, slot, logits=None, dxa=None, dxb=None, dW=None,
              db=None, gscale=None):
     do_bwd = dxa is not None
