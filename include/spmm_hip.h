@@ -365,6 +365,29 @@ int spmm_mpm_head(const void* h, int Lp, int H, const float* w, const float* bia
  * (SPMM_models.py:36-43; d_smiles2pv.py:15-25, d_pv2smiles_batched.py:25-27). */
 int spmm_rows_linear(const void* x, int x_is_bf16, long ldx, const float* W, const float* bias, float* out, long ldo, long rows,
                      int N, int K, int act, spmm_stream_t stream);
+/* Retrieval (csrc/retrieve.hip): the k most similar library rows of every query, streamed -- the [Q, n] similarity matrix of
+ * SPMM_models.py:108-111 (feat @ feat_all) is never formed.  q: fp32 [Q, E], row stride ldq; f: fp32 [n, E], row stride ldf, ONE CHUNK of a
+ * library whose row i has the library index base + i.  State (in/out): scores fp32 [Q, k] and index int64 [Q, k], contiguous.
+ *   merge = 0: the state is overwritten with the chunk's k best;  merge = 1: the chunk's candidates are merged with the state already there
+ *   (chunks of one library must not overlap: an index offered twice is kept twice).
+ * Contract: row j of scores / index holds the k largest q_j . f_i over every row seen so far, largest first, equal scores by ascending
+ * library index; slots beyond the number of rows seen hold (-inf, -1); a NaN similarity ranks below every number (and above an empty
+ * slot, so it is returned only when fewer than k numbers exist).  -0 and +0 are equal scores (returned as +0).  The sum over E has one fixed order
+ * per (query, row) pair -- one exact-f32 MFMA accumulator chain (v_mfma_f32_16x16x4_f32, a k-ordered fmaf chain: one rounding per product,
+ * fp32-grade) that does not depend on the row's place in a tile, a chunk or the grid -- so streaming a library in ANY chunking gives
+ * bit-identical scores and identical indices to one call over the whole library, and two launches on the same inputs agree bit for bit.
+ * No floating-point atomics.
+ * cut_scores fp32 [Q] / cut_index int64 [Q] (optional, both or neither): only chunk rows that rank strictly BELOW the candidate
+ * (cut_scores[j], cut_index[j]) are eligible for query j (none when cut_index[j] < 0) -- the next 64 of a ranking longer than 64: a second
+ * pass over the library with the last entry of the first pass as the cut.  The state read by merge = 1 is not filtered.
+ * workspace: spmm_sim_topk_workspace_bytes(Q, n, k) bytes, 16-byte aligned, private to the call until it completes on `stream` (the
+ * per-workgroup partial lists between the scan launch and the merge launch); not needed when n = 0.
+ * Limits, reported as bad arguments: 1 <= k <= 64; E a multiple of 64 up to 512; Q >= 1; 0 <= n <= 2^31 - 256 rows per chunk (n = 0 with
+ * merge = 1 leaves the state as it is, with merge = 0 it empties the state); q, f 16-byte aligned; ldq, ldf multiples of 4, at least E;
+ * base >= 0. */
+long spmm_sim_topk_workspace_bytes(int Q, long n, int k);
+int spmm_sim_topk(const float* q, long ldq, const float* f, long ldf, long base, int Q, long n, int E, int k, float* scores, long* index,
+                  int merge, const float* cut_scores, const long* cut_index, void* workspace, long workspace_bytes, spmm_stream_t stream);
 /* _dequeue_and_enqueue SPMM_models.py:272-286 (+ the bf16 GEMM shadows of the queue).  skip_flag (optional, device int): when
  * non-zero neither the queue nor the pointer is touched -- the reference's NaN guard returns before the enqueue
  * (SPMM_models.py:132-134 vs :208), so a non-finite momentum feature never enters the queue. */

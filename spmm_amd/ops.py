@@ -437,6 +437,34 @@ def rows_linear(x, W, bias, out, *, act=0):
     return out
 
 
+SIM_TOPK_MAXK = 64      # spmm_sim_topk keeps one candidate per lane of a wave
+
+
+def sim_topk_workspace(Q, n, k, device):
+    """Workspace of one spmm_sim_topk call over a chunk of up to n rows (bytes, 16-byte aligned)."""
+    nbytes = 16 if _DRY_RUN else lib().cdll.spmm_sim_topk_workspace_bytes(int(Q), int(n), int(k))
+    return torch.empty(max(16, nbytes), dtype=torch.uint8, device=device)
+
+
+def sim_topk(q, f, scores, index, *, base=0, merge=False, cut=None, ws=None):
+    """Streaming top-k of q [Q, E] against one chunk f [n, E] of a library (csrc/retrieve.hip): the state scores fp32 [Q, k] / index int64
+    [Q, k] is overwritten with the chunk's k best (merge False) or merged with them (merge True); library index of chunk row i = base + i.
+    cut = (fp32 [Q], int64 [Q]): only rows ranking strictly below that candidate are eligible.  ws: sim_topk_workspace(...) or None."""
+    Q, E = q.shape
+    n = f.shape[0]
+    k = scores.shape[1]
+    assert q.dtype == torch.float32 and f.dtype == torch.float32 and (n == 0 or f.shape[1] == E)
+    assert scores.dtype == torch.float32 and index.dtype == torch.int64 and tuple(scores.shape) == tuple(index.shape) == (Q, k)
+    assert scores.is_contiguous() and index.is_contiguous()
+    cs, ci = (None, None) if cut is None else cut
+    assert cut is None or (cs.dtype == torch.float32 and ci.dtype == torch.int64 and cs.numel() == ci.numel() == Q and cs.is_contiguous() and ci.is_contiguous())
+    if ws is None and n > 0:
+        ws = sim_topk_workspace(Q, n, k, q.device)
+    _call("spmm_sim_topk", _p(q), _row_stride(q), _p(f) if n > 0 else None, _row_stride(f) if n > 0 else E, int(base), Q, n, E, k, _p(scores),
+          _p(index), int(bool(merge)), _p(cs), _p(ci), _p(ws), 0 if ws is None else ws.numel(), _st())
+    return scores, index
+
+
 def enqueue(feats, queue, w3, qT, ptr, *, Bloc, advance=True, skip_flag=None):
     n, E = feats.shape
     _call("spmm_enqueue", _p(feats), n, E, _p(queue), queue.shape[1], _p(w3), _p(qT), _row_stride(qT), Bloc, _p(ptr),

@@ -1,0 +1,338 @@
+"""Property-to-molecule retrieval on the engine: which molecules of a library have these properties?
+
+Two stages, as ALBEF (whose fusion passes the reference's xbert.py carries) retrieves:
+
+  1. shortlist by the contrastive similarity the pretraining aligns (SPMM_models.py:92-131): `pv_features` / `smiles_features` are
+     F.normalize(property_proj / text_proj (position 0 of the unimodal encoder)), and `MoleculeIndex.search` is a streaming top-k of the
+     query features against the library's on csrc/retrieve.hip -- the [Q, N] similarity matrix is never formed;
+  2. re-rank the head of the shortlist with the matching head (SPMM_models.py:137-152, 199-202): `match_scores` runs the two fusion passes
+     of every (query, molecule) pair -- every distinct molecule's text encoded once on packed rows, the cross-attention keys | values of
+     both directions projected once per distinct source per fusion layer, the last fusion layer on the position-0 rows only -- and returns
+     softmax(itm_head(cat(cls_p, cls_t)))[:, 1].
+
+Inference only: no tape, dropout off.  `similar` is the same search with text features as queries (the t2t similarity of :111)."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .engine import BF, Batch, Group, KVSource, SelfKV, host_token_count
+
+TP = "text_encoder.bert."
+MAX_LENGTH = 100                  # tokens per molecule, as the reference's inference scripts truncate (d_smiles2pv.py:43)
+
+
+def _engine(model):
+    eng = getattr(model, "engine", None)
+    if eng is None:
+        raise TypeError(f"spmm_amd.retrieve needs a model with an engine (spmm_amd.model.SPMM); {type(model).__name__} has none -- the retrieval "
+                        "paths are HIP kernels and have no CPU / eager fallback")
+    eng.train_mode = False
+    return eng
+
+
+def _normalized(eng, proj: str, X: torch.Tensor, L: int, B: int, cls_rows=None) -> torch.Tensor:
+    """F.normalize(proj(position 0)) of B sequences of X.  The projection reads the fp32 master weights (spmm_rows_linear, as the module
+    facades `text_proj` / `property_proj` do): the training step's bf16 weight shadow put the features 2.6 x further from the fp32
+    reference than the facade composite (1.0e-4 against 4.0e-5 on the tiny configuration), and a feature is computed once per molecule."""
+    H, E = X.shape[1], eng.cfg.embed_dim
+    cls = X.index_select(0, cls_rows) if cls_rows is not None else X.view(-1, L * H)[:B, :H]
+    raw = ops.rows_linear(cls, eng.P.w(proj + ".weight"), eng.P.w(proj + ".bias"), torch.empty(B, E, dtype=torch.float32, device=X.device))
+    feat = torch.empty(B, E, dtype=torch.float32, device=X.device)
+    ops.l2norm_fwd(raw, feat, torch.empty(B, dtype=torch.float32, device=X.device))
+    return feat
+
+
+def _encode_text(eng, cfg, ids: torch.Tensor, mask: torch.Tensor):
+    """The unimodal text layers on the valid rows of a batch -> (rows [M, H] bf16, pack plan or None, Batch, row of position 0 [B])."""
+    ct, dev = cfg.text, eng.dev
+    B, Lt = ids.shape
+    if Lt > ct.max_position_embeddings:
+        raise ValueError(f"sequence length {Lt} exceeds the {ct.max_position_embeddings} position embeddings")
+    ids32 = ids.to(dev).to(torch.int32).contiguous()
+    mask32 = mask.to(dev).to(torch.int32).contiguous()
+    x, _ = eng.embed_text(TP, ct, ids32, B, Lt, False)
+    pk = eng._pack_plan(mask32, B, Lt, host_token_count(mask)) if (eng.pack_text and Lt <= ops.ATTN_MAXL) else None
+    x, g, cls_rows = eng.text_rows(x, mask32, pk)
+    text, _, _ = eng.stack_fwd(TP, ct, range(0, ct.fusion_layer), False, x, g, False)
+    return text, pk, g, cls_rows
+
+
+@torch.no_grad()
+def smiles_features(model, ids: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """text_feat of SPMM_models.py:93-95 for a batch of token ids [B, Lt] (position 0 = the '[CLS]' token) -> fp32 [B, E], unit rows."""
+    eng = _engine(model)
+    text, _, _, cls_rows = _encode_text(eng, model.cfg, ids, mask)
+    return _normalized(eng, "text_proj", text, ids.shape[1], ids.shape[0], cls_rows=cls_rows)
+
+
+@torch.no_grad()
+def pv_features(model, pv: torch.Tensor, prop_mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """prop_feat of SPMM_models.py:82-92 without the MPM draw: pv [Q, n_props] (normalised values); prop_mask ([n_props] or [Q, n_props],
+    1 = property unknown) puts the learned `property_mask` token at those entries, as conditional generation does
+    (decode.encode_properties).  -> (fp32 [Q, E] unit rows, the PV encoder's hidden states bf16 [Q, n_props + 1, H] for `match_scores`)."""
+    eng = _engine(model)
+    cfg, dev = model.cfg, eng.dev
+    cp, Lp = cfg.prop, cfg.n_props + 1
+    pv = pv.to(dev).to(torch.float32).reshape(-1, cfg.n_props).contiguous()
+    Q = pv.shape[0]
+    if prop_mask is None:
+        pm = torch.zeros(Q, cfg.n_props, dtype=torch.float32, device=dev)
+    else:
+        pm = prop_mask.to(dev).to(torch.float32).reshape(-1, cfg.n_props).expand(Q, cfg.n_props).contiguous()
+    x, _ = eng.embed_pv("property_encoder.", cp, pv, pm, Q, Q, False)
+    y, _, _ = eng.stack_fwd("property_encoder.", cp, range(cp.num_hidden_layers), False, x, Batch([Group(0, Q, Lp, None, Q)]), False)
+    return _normalized(eng, "property_proj", y, Lp, Q), y.view(Q, Lp, cp.hidden_size)
+
+
+# ------------------------------------------------------------------------------------------------------------------ stage one
+def encode_smiles(tokenizer, smiles: Sequence[str], max_length: int = MAX_LENGTH) -> List[List[int]]:
+    """Token ids as the text encoder sees them at inference (d_smiles2pv.py:40-44): the string starts with the text '[CLS]', the
+    tokenizer's own [CLS] is dropped."""
+    return [tokenizer.encode(s if s.startswith("[CLS]") else "[CLS]" + s, max_length)[1:] for s in smiles]
+
+
+def pad_rows(rows: Sequence[Sequence[int]], pad_id: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    L = max(len(r) for r in rows)
+    ids = torch.full((len(rows), L), pad_id, dtype=torch.long)
+    for i, r in enumerate(rows):
+        ids[i, :len(r)] = torch.as_tensor(r, dtype=torch.long)
+    return ids, (ids != pad_id).long()
+
+
+def length_sorted_batches(lengths, batch_size: int):
+    order = np.argsort(np.asarray(lengths), kind="stable")
+    return [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+
+
+def topk_reference(q: torch.Tensor, feats: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The tensor-library pair the kernel replaces: torch.topk(q @ feats.T, k) -- forms the [Q, N] matrix.  Yard-stick of the bench."""
+    v, i = torch.topk(q @ feats.T, min(k, feats.shape[0]), dim=1)
+    return v, i
+
+
+class MoleculeIndex:
+    """The text features of a library, fp32 [N, E] on the device in INPUT order, and -- when built from tokens -- the padded token ids the
+    re-ranking stage needs (host tensors)."""
+
+    def __init__(self, feats: torch.Tensor, ids: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                 smiles: Optional[List[str]] = None):
+        assert feats.dim() == 2 and feats.dtype == torch.float32
+        self.feats, self.ids, self.mask, self.smiles = feats.contiguous(), ids, mask, smiles
+
+    def __len__(self):
+        return self.feats.shape[0]
+
+    @classmethod
+    @torch.no_grad()
+    def from_tokens(cls, model, ids: torch.Tensor, mask: torch.Tensor, batch_size: int = 256, smiles=None) -> "MoleculeIndex":
+        """ids / mask [N, L] (host or device; zero padded prefixes): batches in order of token length, each cut to its longest molecule,
+        features written back in input order."""
+        eng = _engine(model)
+        ids_h, mask_h = ids.cpu(), mask.cpu()
+        N = ids_h.shape[0]
+        feats = torch.empty(N, model.cfg.embed_dim, dtype=torch.float32, device=eng.dev)
+        lens = mask_h.sum(1)
+        for idx in length_sorted_batches(lens.numpy(), batch_size):
+            sel = torch.from_numpy(idx)
+            L = max(1, int(lens[sel].max()))
+            feats[sel.to(eng.dev)] = smiles_features(model, ids_h[sel, :L], mask_h[sel, :L])
+        return cls(feats, ids_h, mask_h, smiles)
+
+    @classmethod
+    def build(cls, model, tokenizer, smiles: Sequence[str], batch_size: int = 256) -> "MoleculeIndex":
+        rows = encode_smiles(tokenizer, smiles)
+        ids, mask = pad_rows(rows, tokenizer.pad_token_id)
+        return cls.from_tokens(model, ids, mask, batch_size, smiles=list(smiles))
+
+    def save(self, path: str) -> None:
+        torch.save({"format": "spmm_amd.MoleculeIndex/1", "feats": self.feats.cpu(), "ids": self.ids, "mask": self.mask, "smiles": self.smiles}, path)
+
+    @classmethod
+    def load(cls, path: str, device="cuda") -> "MoleculeIndex":
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        if d.get("format") != "spmm_amd.MoleculeIndex/1":
+            raise ValueError(f"{path}: not a saved MoleculeIndex")
+        return cls(d["feats"].to(device), d["ids"], d["mask"], d["smiles"])
+
+    @torch.no_grad()
+    def search(self, query_feats: torch.Tensor, k: int, chunk: int = 1 << 20) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The k most similar library rows of every query -> (scores fp32 [Q, k], index int64 [Q, k]): largest first, equal scores by
+        ascending index, (-inf, -1) beyond the library's size.  The library is streamed `chunk` rows at a time through spmm_sim_topk
+        (any chunking gives the same bits); a ranking longer than the kernel's 64 slots takes one more pass over the library per further
+        64, each cut at the last entry of the pass before."""
+        q = query_feats.to(self.feats.device).to(torch.float32)
+        if q.dim() != 2 or q.shape[1] != self.feats.shape[1]:
+            raise ValueError(f"query features {tuple(q.shape)} do not match the library's {tuple(self.feats.shape)}")
+        if k < 1 or chunk < 1:
+            raise ValueError(f"k={k} chunk={chunk}")
+        if q.stride(1) != 1 or q.stride(0) % 4 or q.data_ptr() % 16:
+            q = q.contiguous()
+        Q, N, dev = q.shape[0], self.feats.shape[0], q.device
+        K = ops.SIM_TOPK_MAXK
+        # one workspace for the launches of THIS search (they are ordered on the current stream; sized for its largest chunk and pass):
+        # nothing is shared between two searches, so an index may be searched from several streams at once
+        ws = ops.sim_topk_workspace(Q, min(N, chunk), min(k, K), dev)
+        out_s, out_i, cut = [], [], None
+        for k0 in range(0, k, K):
+            kk = min(K, k - k0)
+            s = torch.empty(Q, kk, dtype=torch.float32, device=dev)
+            i = torch.empty(Q, kk, dtype=torch.int64, device=dev)
+            ops.sim_topk(q, self.feats[:min(N, chunk)], s, i, base=0, merge=False, cut=cut, ws=ws if N > 0 else None)
+            for r0 in range(chunk, N, chunk):
+                ops.sim_topk(q, self.feats[r0:r0 + chunk], s, i, base=r0, merge=True, cut=cut, ws=ws)
+            out_s.append(s)
+            out_i.append(i)
+            cut = (s[:, kk - 1].contiguous(), i[:, kk - 1].contiguous())
+        return (out_s[0], out_i[0]) if len(out_s) == 1 else (torch.cat(out_s, 1), torch.cat(out_i, 1))
+
+
+# ------------------------------------------------------------------------------------------------------------------ stage two
+def _host_lens(mask_h: torch.Tensor) -> np.ndarray:
+    lens = mask_h.sum(1)
+    L = mask_h.shape[1]
+    prefix = bool((lens > 0).all()) and bool(((torch.arange(L)[None, :] < lens[:, None]) == (mask_h != 0)).all())
+    if not prefix:
+        raise ValueError("match_scores: every attention mask must be a non-empty prefix (what padding a batch to its longest gives)")
+    return lens.numpy().astype(np.int64)
+
+
+@torch.no_grad()
+def match_scores(model, pv_hidden: torch.Tensor, ids: torch.Tensor, mask: torch.Tensor, pairs: torch.Tensor, engine: bool = True) -> torch.Tensor:
+    """Matching probability of P (query, molecule) pairs: pairs int64 [P, 2] = (row of pv_hidden, row of ids / mask) -> fp32 [P] =
+    softmax(itm_head(cat(cls_p, cls_t)))[:, 1] (SPMM_models.py:137-152, 199-202), cls_p = position 0 of the fusion layers over the PV
+    states cross-attending the molecule's text, cls_t = position 0 of the fusion layers over the text cross-attending the PV states.
+
+    engine=True: the text of every distinct molecule is encoded once on packed rows; the keys | values of both cross-attention directions
+    are projected once per distinct source per fusion layer (engine.KVSource: the P PV-query sequences are bound to their molecule's text,
+    the P text-query sequences to their query's PV states); the last fusion layer runs on the 2 P position-0 rows, its self-attention
+    keys / values projected from the full sequences of the layer below (engine.SelfKV); the head is spmm_rows_linear.
+    engine=False: the same arithmetic the way the reference runs it -- the dense module calls `text_encoder.bert(mode='text')` and the two
+    `text_encoder.bert(mode='fusion')` on the P pairs as a padded batch, every molecule encoded once per pair it occurs in: the yard-stick."""
+    pairs_h = pairs.cpu().to(torch.int64).reshape(-1, 2)
+    P = pairs_h.shape[0]
+    ids_h, mask_h = ids.cpu(), mask.cpu()
+    if P == 0:
+        return torch.empty(0, dtype=torch.float32, device=pv_hidden.device)
+    if int(pairs_h[:, 0].min()) < 0 or int(pairs_h[:, 0].max()) >= pv_hidden.shape[0] or int(pairs_h[:, 1].min()) < 0 or int(pairs_h[:, 1].max()) >= ids_h.shape[0]:
+        raise IndexError("match_scores: a pair names a query or a molecule that is not there")
+    if not engine:
+        return _match_dense(model, pv_hidden, ids_h, mask_h, pairs_h)
+    eng = _engine(model)
+    cfg, dev = model.cfg, eng.dev
+    ct = cfg.text
+    H, Lp, f, n = ct.hidden_size, cfg.n_props + 1, ct.fusion_layer, ct.num_hidden_layers
+    qs, inv_q = torch.unique(pairs_h[:, 0], return_inverse=True)
+    ms, inv_m = torch.unique(pairs_h[:, 1], return_inverse=True)
+    Up, Ut = qs.numel(), ms.numel()
+    # ---- every distinct molecule's text, once, on packed rows (cut to the longest of them)
+    lens_u = _host_lens(mask_h[ms])
+    Lt = int(lens_u.max())
+    if Lt > ops.ATTN_MAXL:
+        raise ValueError(f"match_scores: a molecule of {Lt} tokens exceeds the {ops.ATTN_MAXL} the packed attention layouts hold")
+    text, pk, _, _ = _encode_text(eng, cfg, ids_h[ms, :Lt], mask_h[ms, :Lt])
+    row0_u = np.concatenate([[0], np.cumsum(lens_u)[:-1]]) if pk else np.arange(Ut, dtype=np.int64) * Lt      # (dense: every molecule is Lt long)
+    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)                        # noqa: E731
+    i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)                        # noqa: E731
+    src_text = KVSource(text, Ut, Lt, row0=i32(row0_u), length=i32(lens_u))
+    pvh = pv_hidden.to(dev).to(BF)[qs.to(dev)].reshape(Up * Lp, H).contiguous()
+    src_pv = KVSource(pvh, Up, Lp)
+    # ---- the fusion batch: [P PV-query sequences, dense | P text-query sequences, packed]
+    iq, im = inv_q.numpy(), inv_m.numpy()
+    len_p = lens_u[im]
+    qrow0 = np.concatenate([[0], np.cumsum(len_p)[:-1]])
+    Mt = int(len_p.sum())
+    o_t = P * Lp
+    gat_pv = (iq[:, None] * Lp + np.arange(Lp)[None, :]).reshape(-1)
+    gat_tx = np.concatenate([row0_u[u] + np.arange(l) for u, l in zip(im, len_p)])
+    X = torch.cat([pvh.index_select(0, i64(gat_pv)), text.index_select(0, i64(gat_tx))])
+    kv_m, kv_q = i32(im), i32(iq)
+    qrow0_d, qlen_d = i32(qrow0), i32(len_p)
+    g_lo = Batch([Group(0, P, Lp, None, P).bind(src_text, kv_m, 0),
+                  Group(o_t, P, Lt, None, P, q_row0=qrow0_d, q_len=qlen_d, nrows=Mt).bind(src_pv, kv_q, 0)])
+    y, _, _ = eng.stack_fwd(TP, ct, range(f, n - 1), True, X, g_lo, False)
+    # ---- the last fusion layer on the 2 P position-0 rows; self-attention keys / values from every row of the layer below
+    top_rows = np.concatenate([np.arange(P, dtype=np.int64) * Lp, o_t + qrow0])
+    xt = y.index_select(0, i64(top_rows))
+    skv = SelfKV(y)
+    g_top = Batch([Group(0, P, 1, None, P, self_src=skv, skv_row0=i32(np.arange(P) * Lp), skv_len=i32(np.full(P, Lp)), skv_L=Lp).bind(src_text, kv_m, 0),
+                   Group(P, P, 1, None, P, self_src=skv, skv_row0=i32(o_t + qrow0), skv_len=qlen_d, skv_L=Lt).bind(src_pv, kv_q, 0)])
+    yt, _, _ = eng._layer_fwd(f"{TP}encoder.layer.{n - 1}.", ct, True, xt, g_top, False)
+    vl = torch.cat([yt[:P], yt[P:]], dim=1)                                       # [P, 2H]: cat(cls_p, cls_t) of :201
+    logits = ops.rows_linear(vl, eng.P.w("itm_head.weight"), eng.P.w("itm_head.bias"), torch.empty(P, 2, dtype=torch.float32, device=dev))
+    return torch.softmax(logits, dim=1)[:, 1]
+
+
+def _match_dense(model, pv_hidden, ids_h, mask_h, pairs_h) -> torch.Tensor:
+    """`match_scores(engine=False)`: written against the module API (text_encoder.bert, itm_head), so it runs on any object that has it."""
+    dev = pv_hidden.device
+    m_sel = pairs_h[:, 1]
+    L = max(1, int(mask_h[m_sel].sum(1).max()))
+    ids, mask = ids_h[m_sel, :L].to(dev), mask_h[m_sel, :L].to(dev)
+    pv = pv_hidden[pairs_h[:, 0].to(dev)].float()
+    ones = torch.ones(pv.shape[:2], dtype=torch.long, device=dev)
+    bert = model.text_encoder.bert
+    text = bert(ids, attention_mask=mask, return_dict=True, mode="text").last_hidden_state
+    cls_p = bert(encoder_embeds=pv, attention_mask=ones, encoder_hidden_states=text, encoder_attention_mask=mask, return_dict=True,
+                 mode="fusion").last_hidden_state[:, 0, :]
+    cls_t = bert(encoder_embeds=text, attention_mask=mask, encoder_hidden_states=pv, encoder_attention_mask=ones, return_dict=True,
+                 mode="fusion").last_hidden_state[:, 0, :]
+    logits = model.itm_head(torch.cat([cls_p, cls_t], dim=-1))
+    return torch.softmax(logits.float(), dim=-1)[:, 1]
+
+
+# ------------------------------------------------------------------------------------------------------------------ both stages
+@dataclass
+class Retrieved:
+    """Per query: the k shortlisted library indices (input order of the library; -1 beyond its size) with their cosine similarity; the
+    first `rerank` of them are ordered by matching probability (`match`, NaN for the rest)."""
+    index: torch.Tensor        # int64 [Q, k]
+    cosine: torch.Tensor       # fp32 [Q, k]
+    match: torch.Tensor        # fp32 [Q, k]
+
+
+def _as_index(index_or_feats) -> MoleculeIndex:
+    return index_or_feats if isinstance(index_or_feats, MoleculeIndex) else MoleculeIndex(index_or_feats)
+
+
+@torch.no_grad()
+def retrieve(model, index_or_feats, library_ids, library_mask, pv, prop_mask=None, k: int = 100, rerank: int = 16, chunk: int = 1 << 20) -> Retrieved:
+    """Molecules of the library whose properties match `pv` ([Q, n_props] normalised; prop_mask: 1 = unspecified).  library_ids /
+    library_mask: the library's padded tokens in the index's order (None: the index's own)."""
+    index = _as_index(index_or_feats)
+    library_ids = index.ids if library_ids is None else library_ids
+    library_mask = index.mask if library_mask is None else library_mask
+    qf, hidden = pv_features(model, pv, prop_mask)
+    scores, idx = index.search(qf, k, chunk=chunk)
+    return _rerank(model, hidden, library_ids, library_mask, scores, idx, rerank)
+
+
+def _rerank(model, hidden, library_ids, library_mask, scores, idx, rerank) -> Retrieved:
+    Q, k = idx.shape
+    match = torch.full((Q, k), float("nan"), dtype=torch.float32, device=idx.device)
+    r = min(int(rerank), k)
+    if r > 0:
+        if library_ids is None or library_mask is None:
+            raise ValueError("re-ranking needs the library's token ids and mask (or rerank=0)")
+        head = idx[:, :r].cpu()
+        qq, jj = torch.nonzero(head >= 0, as_tuple=True)
+        if qq.numel():
+            prob = match_scores(model, hidden, library_ids, library_mask, torch.stack([qq, head[qq, jj]], dim=1))
+            match[qq.to(idx.device), jj.to(idx.device)] = prob
+            # matching probability, largest first; equal probabilities keep the shortlist's order; empty slots stay last
+            order = torch.sort(torch.nan_to_num(match[:, :r], nan=-1.0), dim=1, descending=True, stable=True).indices
+            idx, scores, match = idx.clone(), scores.clone(), match.clone()
+            idx[:, :r] = idx[:, :r].gather(1, order)
+            scores[:, :r] = scores[:, :r].gather(1, order)
+            match[:, :r] = match[:, :r].gather(1, order)
+    return Retrieved(idx, scores, match)
+
+
+@torch.no_grad()
+def similar(model, index_or_feats, ids: torch.Tensor, mask: torch.Tensor, k: int, chunk: int = 1 << 20) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Molecule-to-molecule neighbours on the t2t similarity (SPMM_models.py:111): the search with text features as queries."""
+    return _as_index(index_or_feats).search(smiles_features(model, ids, mask), k, chunk=chunk)
