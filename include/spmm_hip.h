@@ -329,6 +329,28 @@ int spmm_lm_loss(const float* logits, const float* logits_m, long ldl, const int
 int spmm_s2s_loss(const float* logits, long ldl, const int* ids, const long* row_of, long rows, long nseq, int L, int V,
                   int* n_label_ws, const float* gscale, void* dlogits, long ldd, int Vpad, float* losses, int loss_slot,
                   spmm_stream_t stream);
+/* Teacher-forced scoring (csrc/score.hip): the vocabulary projection of the tied LM head, log_softmax and the gather of the label's entry
+ * in one launch -- the [rows, V] logits are never written.  y: bf16 [rows, H], row stride ldy, the output of cls.predictions.transform
+ * (Linear, GELU, LayerNorm); Wd: bf16 [V, H], row stride ldw, the decoder weight (= the word-embedding shadow); bias: fp32 [V].
+ * logit[r, v] = bias[v] + sum_h y[r,h] Wd[v,h]: bf16 operands, fp32 accumulation on v_mfma_f32_16x16x32_bf16 (the operand rounding of
+ * spmm_gemm_nt with SPMM_EPI_F32); log p = logit[label] - max - log sum exp(logit - max) in fp32, the row maximum subtracted first.
+ * Labels: the rule of spmm_s2s_loss -- ids int32 [nseq*L], the dense sequences; row r is dense row d = row_of ? row_of[r] : r and predicts
+ * ids[d + 1] unless d % L == L - 1; a label of 0 or outside [0, V) is ignored and never indexes memory.  A scored sequence
+ * [CLS] t1 .. tn [SEP] PAD.. therefore sums over t1 .. tn and [SEP], which is what the beam searches accumulate.
+ * Sequences: seq_row0 / seq_len int32 [nseq] = first row and row count of every sequence (packed rows); both null: dense, sequence s owns
+ * the L rows from s * L (rows == nseq * L).  A sequence's rows are clamped to [0, rows).
+ * Outputs, every element written: tok_lp fp32 [rows] = log p(label) of the row, 0 where the row has no label; seq_lp fp32 [nseq] = the sum
+ * of the sequence's labelled rows; seq_n int32 [nseq] = their count ((0, 0) for a sequence without a label).
+ * Determinism: no floating-point atomics.  The sum over H of a (row, token) pair is one MFMA accumulator chain over ascending K-slices; it
+ * does not depend on the row's place in a tile, the grid or the batch.  Each row's softmax reduction has one fixed order.  seq_lp is summed
+ * in ascending row order by a second small launch.  So the same y row gives bit-identical tok_lp in any batch, seq_lp[s] is the fp32
+ * left-to-right sum of its tok_lp, and two launches agree bit for bit.
+ * Limits, reported as bad arguments before anything is launched: H a multiple of 64 up to 1024; 2 <= V <= 512; rows >= 1, nseq >= 1, L >= 2,
+ * rows <= nseq * L; ldy, ldw multiples of 8, at least H; y, Wd 16-byte aligned (they are read 16 bytes at a time), the fp32 / int32 arrays
+ * 4-byte and row_of 8-byte aligned; y, Wd, bias, ids, tok_lp, seq_lp, seq_n not null; seq_row0 and seq_len both null or both given. */
+int spmm_lm_score(const void* y, long ldy, const void* Wd, long ldw, const float* bias, const int* ids, const long* row_of, long rows,
+                  long nseq, int L, int V, int H, const int* seq_row0, const int* seq_len, float* tok_lp, float* seq_lp, int* seq_n,
+                  spmm_stream_t stream);
 /* itm_head + cross entropy SPMM_models.py:201-206 (forward and backward in one pass). */
 int spmm_itm_head(const void* xa, long stride_a, const void* xb, long stride_b, int H, const float* W, const float* bias,
                   int n, int B, const float* gscale, float* losses, int loss_slot, float* logits_out, void* dxa, void* dxb,

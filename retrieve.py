@@ -9,7 +9,8 @@ query is given as pv2smiles.py takes it and the library as smiles2pv.py takes it
   python retrieve.py --synthetic 64 --tiny --top_k 5 --rerank 3                  (no data files: seeded weights, library, query, vocabulary)
 
 Stage one shortlists --top_k molecules by the contrastive similarity of the pretraining (spmm_amd.retrieve.MoleculeIndex.search, a streaming
-top-k kernel); stage two re-orders the first --rerank of them by the matching head's probability (spmm_amd.retrieve.match_scores).  The CSV
+top-k kernel); stage two re-orders the first --rerank of them by the matching head's probability (spmm_amd.retrieve.match_scores) or, with --rerank_by likelihood, by log p(SMILES | query) per token (spmm_amd.score.score_smiles; the
+CSV then ends with a logp_per_token column).  The CSV
 has one row per shortlisted molecule: rank, line number in the library (1-based), SMILES, cosine, matching probability (empty beyond
 --rerank and for --query_smiles)."""
 import argparse
@@ -28,20 +29,23 @@ from smiles2pv import read_smiles, synthetic_smiles                        # noq
 N_PROPS = 53
 
 
-def ranked_rows(index_row, cosine_row, match_row, smiles):
-    """One query's result -> [(rank, library line number, SMILES, cosine, matching probability or '')], empty slots dropped."""
+def ranked_rows(index_row, cosine_row, match_row, smiles, logp_row=None):
+    """One query's result -> [(rank, library line number, SMILES, cosine, matching probability or '')], empty slots dropped; with
+    logp_row (--rerank_by likelihood) every row ends with the log-likelihood per token or ''."""
     rows = []
-    for i, c, m in zip(index_row.tolist(), cosine_row.tolist(), match_row.tolist()):
+    extra = [None] * len(index_row) if logp_row is None else logp_row.tolist()
+    for i, c, m, lp in zip(index_row.tolist(), cosine_row.tolist(), match_row.tolist(), extra):
         if i < 0:
             continue
-        rows.append((len(rows) + 1, i + 1, smiles[i] if smiles is not None else "", repr(float(c)), "" if m != m else repr(float(m))))
+        row = (len(rows) + 1, i + 1, smiles[i] if smiles is not None else "", repr(float(c)), "" if m != m else repr(float(m)))
+        rows.append(row if logp_row is None else row + ("" if lp != lp else repr(float(lp)),))
     return rows
 
 
-def write_csv(path: str, rows):
+def write_csv(path: str, rows, likelihood: bool = False):
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["rank", "library_line", "smiles", "cosine", "match_probability"])
+        w.writerow(["rank", "library_line", "smiles", "cosine", "match_probability"] + (["logp_per_token"] if likelihood else []))
         w.writerows(rows)
 
 
@@ -118,13 +122,13 @@ def main(args):
     if args.query_smiles:
         ids, mask = R.pad_rows(R.encode_smiles(tokenizer, [args.query_smiles]), tokenizer.pad_token_id)
         cosine, idx = R.similar(model, index, ids, mask, args.top_k)
-        match = torch.full_like(cosine, float("nan"))
+        match, logp = torch.full_like(cosine, float("nan")), None
     else:
         pv = prop_input if norm is None or args.synthetic else (prop_input - norm[0]) / norm[1]
-        res = R.retrieve(model, index, None, None, pv.reshape(1, -1), prop_mask, k=args.top_k, rerank=args.rerank)
-        idx, cosine, match = res.index, res.cosine, res.match
-    rows = ranked_rows(idx[0].cpu(), cosine[0].cpu(), match[0].cpu(), index.smiles)
-    write_csv(args.output, rows)
+        res = R.retrieve(model, index, None, None, pv.reshape(1, -1), prop_mask, k=args.top_k, rerank=args.rerank, rerank_by=args.rerank_by)
+        idx, cosine, match, logp = res.index, res.cosine, res.match, res.logp_per_token
+    rows = ranked_rows(idx[0].cpu(), cosine[0].cpu(), match[0].cpu(), index.smiles, None if logp is None else logp[0].cpu())
+    write_csv(args.output, rows, likelihood=logp is not None)
     for r in rows[:10]:
         print("%4d  line %-8d cosine %s  match %s  %s" % (r[0], r[1], r[3][:9], r[4][:9] or "-", r[2]))
     print(f"{len(rows)} molecules are saved in '{args.output}'")
@@ -149,6 +153,9 @@ def parse_args(argv=None):
     # the search
     p.add_argument("--top_k", default=100, type=int, help="molecules shortlisted by contrastive similarity")
     p.add_argument("--rerank", default=16, type=int, help="head of the shortlist re-ordered by matching probability (0: none)")
+    p.add_argument("--rerank_by", default="match", choices=("match", "likelihood"),
+                   help="what orders the head of the shortlist: the matching head's probability, or log p(SMILES | query) per token "
+                        "(spmm_amd.score.score_smiles; the CSV gains a logp_per_token column)")
     p.add_argument("--batch_size", default=256, type=int, help="molecules encoded together when the index is built")
     p.add_argument("--output", default="retrieved_molecules.csv", help="CSV: rank, library line number, SMILES, cosine, matching probability")
     p.add_argument("--seed", default=0, type=int, help="seed of --synthetic's weights, library and query")

@@ -372,6 +372,34 @@ def s2s_loss(logits, ids, *, nseq, L, V, ws, losses, slot, row_of=None, dlogits=
           0 if dlogits is None else _row_stride(dlogits), V if dlogits is None else dlogits.shape[1], _p(losses), slot, _st())
 
 
+LM_SCORE_MAXV = 512     # spmm_lm_score keeps a row's whole logit strip in registers
+
+
+def lm_score(y, Wd, bias, ids, *, nseq, L, row_of=None, seq_row0=None, seq_len=None, tok_lp=None, seq_lp=None, seq_n=None):
+    """log p(label) of every row of y under the tied LM head without the logits (csrc/score.hip): y bf16 [rows, H] (row stride free), Wd
+    bf16 [V, H], bias fp32 [V]; ids int32 [nseq*L] and row_of int64 [rows] follow the label rule of `s2s_loss`; seq_row0 / seq_len int32
+    [nseq] give every sequence's rows (packed), both None: dense rows.  -> (tok_lp fp32 [rows], seq_lp fp32 [nseq], seq_n int32 [nseq]);
+    every element is written."""
+    rows, H = y.shape
+    V = Wd.shape[0]
+    dev = y.device
+    assert y.dtype == BF16 and Wd.dtype == BF16 and Wd.shape[1] >= H and y.stride(1) == 1 and Wd.stride(1) == 1
+    assert bias.dtype == torch.float32 and bias.numel() == V and bias.is_contiguous()
+    assert ids.dtype == torch.int32 and ids.numel() == nseq * L and ids.is_contiguous()
+    assert row_of is None or (row_of.dtype == torch.int64 and row_of.numel() >= rows and row_of.is_contiguous())
+    assert (seq_row0 is None) == (seq_len is None)
+    assert seq_row0 is None or all(t.dtype == torch.int32 and t.numel() == nseq and t.is_contiguous() for t in (seq_row0, seq_len))
+    tok_lp = torch.empty(rows, dtype=torch.float32, device=dev) if tok_lp is None else tok_lp
+    seq_lp = torch.empty(nseq, dtype=torch.float32, device=dev) if seq_lp is None else seq_lp
+    seq_n = torch.empty(nseq, dtype=torch.int32, device=dev) if seq_n is None else seq_n
+    assert tok_lp.dtype == torch.float32 and tok_lp.numel() == rows and tok_lp.is_contiguous()
+    assert seq_lp.dtype == torch.float32 and seq_lp.numel() == nseq and seq_lp.is_contiguous()
+    assert seq_n.dtype == torch.int32 and seq_n.numel() == nseq and seq_n.is_contiguous()
+    _call("spmm_lm_score", _p(y), _row_stride(y), _p(Wd), _row_stride(Wd), _p(bias), _p(ids), _p(row_of), rows, nseq, L, V, H, _p(seq_row0),
+          _p(seq_len), _p(tok_lp), _p(seq_lp), _p(seq_n), _st())
+    return tok_lp, seq_lp, seq_n
+
+
 def itm_head(xa, stride_a, xb, stride_b, H, W, bias, *, n, B, losses, slot, logits=None, dxa=None, dxb=None, dW=None,
              db=None, gscale=None):
     do_bwd = dxa is not None

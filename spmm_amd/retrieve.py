@@ -289,10 +289,12 @@ def _match_dense(model, pv_hidden, ids_h, mask_h, pairs_h) -> torch.Tensor:
 @dataclass
 class Retrieved:
     """Per query: the k shortlisted library indices (input order of the library; -1 beyond its size) with their cosine similarity; the
-    first `rerank` of them are ordered by matching probability (`match`, NaN for the rest)."""
+    first `rerank` of them are ordered by matching probability (`match`, NaN for the rest) or -- rerank_by='likelihood' -- by the
+    teacher-forced log-likelihood per token under the query (`logp_per_token`, NaN for the rest; `match` is then all NaN)."""
     index: torch.Tensor        # int64 [Q, k]
     cosine: torch.Tensor       # fp32 [Q, k]
     match: torch.Tensor        # fp32 [Q, k]
+    logp_per_token: Optional[torch.Tensor] = None      # fp32 [Q, k], rerank_by='likelihood' only
 
 
 def _as_index(index_or_feats) -> MoleculeIndex:
@@ -300,15 +302,44 @@ def _as_index(index_or_feats) -> MoleculeIndex:
 
 
 @torch.no_grad()
-def retrieve(model, index_or_feats, library_ids, library_mask, pv, prop_mask=None, k: int = 100, rerank: int = 16, chunk: int = 1 << 20) -> Retrieved:
+def retrieve(model, index_or_feats, library_ids, library_mask, pv, prop_mask=None, k: int = 100, rerank: int = 16, chunk: int = 1 << 20,
+             rerank_by: str = "match") -> Retrieved:
     """Molecules of the library whose properties match `pv` ([Q, n_props] normalised; prop_mask: 1 = unspecified).  library_ids /
-    library_mask: the library's padded tokens in the index's order (None: the index's own)."""
+    library_mask: the library's padded tokens in the index's order (None: the index's own).  rerank_by: 'match' orders the head of the
+    shortlist by the matching head's probability, 'likelihood' by log p(SMILES | PV) per token (spmm_amd.score.score_smiles)."""
+    if rerank_by not in ("match", "likelihood"):
+        raise ValueError(f"rerank_by={rerank_by!r}: 'match' or 'likelihood'")
     index = _as_index(index_or_feats)
     library_ids = index.ids if library_ids is None else library_ids
     library_mask = index.mask if library_mask is None else library_mask
     qf, hidden = pv_features(model, pv, prop_mask)
     scores, idx = index.search(qf, k, chunk=chunk)
+    if rerank_by == "likelihood":
+        return _rerank_likelihood(model, pv, prop_mask, library_ids, library_mask, scores, idx, rerank)
     return _rerank(model, hidden, library_ids, library_mask, scores, idx, rerank)
+
+
+def _rerank_likelihood(model, pv, prop_mask, library_ids, library_mask, scores, idx, rerank) -> Retrieved:
+    from .score import score_smiles
+    Q, k = idx.shape
+    nan = torch.full((Q, k), float("nan"), dtype=torch.float32, device=idx.device)
+    per = nan.clone()
+    r = min(int(rerank), k)
+    if r > 0:
+        if library_ids is None or library_mask is None:
+            raise ValueError("re-ranking needs the library's token ids and mask (or rerank=0)")
+        head = idx[:, :r].cpu()
+        qq, jj = torch.nonzero(head >= 0, as_tuple=True)
+        if qq.numel():
+            sc = score_smiles(model, pv.reshape(Q, -1), library_ids, library_mask, pairs=torch.stack([qq, head[qq, jj]], dim=1), prop_mask=prop_mask)
+            per[qq.to(idx.device), jj.to(idx.device)] = sc.per_token().to(idx.device)
+            # log-likelihood per token, largest first; equal values keep the shortlist's order; empty slots stay last
+            order = torch.sort(torch.nan_to_num(per[:, :r], nan=-float("inf")), dim=1, descending=True, stable=True).indices
+            idx, scores = idx.clone(), scores.clone()
+            idx[:, :r] = idx[:, :r].gather(1, order)
+            scores[:, :r] = scores[:, :r].gather(1, order)
+            per[:, :r] = per[:, :r].gather(1, order)
+    return Retrieved(idx, scores, nan, per)
 
 
 def _rerank(model, hidden, library_ids, library_mask, scores, idx, rerank) -> Retrieved:
