@@ -37,13 +37,16 @@ const char* spmm_last_error(void);
 /* epilogues of spmm_gemm_nt */
 #define SPMM_EPI_BF16 0        /* C(bf16) = alpha*acc/(*div) + bias + R                                  */
 #define SPMM_EPI_GELU 1        /* C2(bf16) = pre = acc + bias ; C(bf16) = gelu_erf(pre)                  */
-#define SPMM_EPI_F32 2         /* C(f32)  = alpha*acc/(*div) + bias                                      */
-#define SPMM_EPI_F32_ATOMIC 3  /* C(f32) += alpha*acc  with atomicAdd (split-K allowed)                  */
+#define SPMM_EPI_F32 2         /* C(f32)  = alpha*acc/(*div) + bias + R                                  */
+#define SPMM_EPI_F32_ATOMIC 3  /* C(f32) += alpha*acc/(*div) + bias + R  with atomicAdd (split-K allowed) */
 #define SPMM_EPI_GELU_GRAD 4   /* C(bf16) = acc * gelu_erf'(G)                                           */
-#define SPMM_EPI_F32_ACC 5     /* C(f32) += alpha*acc + bias   (plain read-modify-write, single owner)   */
+#define SPMM_EPI_F32_ACC 5     /* C(f32) += alpha*acc/(*div) + bias + R   (plain read-modify-write, single owner) */
 #define SPMM_EPI_GELU_DERIV 6  /* pre = acc + bias ; C(bf16) = gelu_erf(pre) ; C2(bf16) = gelu_erf'(pre): the FFN forward keeps  */
                                /* the derivative (one shared exp) so that the backward epilogue is SPMM_EPI_MUL                  */
 #define SPMM_EPI_MUL 7         /* C(bf16) = alpha*acc * G      (G bf16, e.g. the stored gelu'; colsum allowed)                   */
+/* The three fp32-output epilogues take bias (fp32 [N]) and R (bf16 [M, ldr], ldr % 4 == 0, 8-B aligned) like SPMM_EPI_BF16; acc is the
+ * whole K reduction: under split-K (SPMM_EPI_F32_ATOMIC, splits > 1) every K-slice adds alpha/(*div) times its partial sum and bias and
+ * R are added exactly ONCE per element (by the first slice), whatever `splits` is. */
 
 /* C[M,N] = A[M,K] . W[N,K]^T on MFMA (bf16 in, fp32 accumulate).  Replaces every nn.Linear on the path
  * (xbert.py:280-300 query/key/value, :370 attention output.dense, :435 intermediate.dense + erf GELU :436,
@@ -71,7 +74,8 @@ const char* spmm_last_error(void);
 int spmm_gemm_nt(const void* A, long lda, const void* W, long ldw, int M, int N, int K, int splits, const float* bias,
                  const float* div_ptr, float alpha, const void* R, long ldr, const void* G, long ldg, void* C, long ldc,
                  void* C2, long ldc2, int epi, float* colsum, int kernel, const int* M_dev, spmm_stream_t stream);
-/* Device-side row counts (`M_dev` / `R_dev` / `rows_dev`, optional, null = none): spmm_gemm_nt (8-phase kernel),
+/* Device-side row counts (`M_dev` / `R_dev` / `rows_dev`, optional, null = none): spmm_gemm_nt (every kernel -- SPMM_GEMM_K128,
+ * SPMM_GEMM_K128PC, SPMM_GEMM_K256x128, SPMM_GEMM_K256, SPMM_GEMM_K256P8 / _TILES, chosen or forced -- and every epilogue, split-K too),
  * spmm_gemm_tn (8-phase kernel, split launch), spmm_colsum_bf16, spmm_ln_fwd and spmm_ln_bwd take a pointer to an int in device memory
  * holding the number of rows to process, <= the host-side row count the launch and the buffers are sized for.  Rows past it are neither
  * read nor written.  For batches whose tail length only the device knows -- here the text hard negatives drawn on the device

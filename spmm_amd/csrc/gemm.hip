@@ -42,7 +42,7 @@ struct GemmP {
   bf16* C2; long ldc2;       // EPI_GELU: pre-activation output; EPI_GELU_DERIV: gelu'(pre-activation)
   float* colsum;             // optional: colsum[n] += sum_m C[m][n] of the (bf16-rounded) output -- bias gradient of the producing layer
   int order;                 // tile order inside an XCD's range (tile_of): 0 row-major, 3 row-major inside 2 column groups
-  // optional device-side row count (8-phase kernel only): the launch is SIZED for M rows, the kernel computes *M_ptr <= M of them -- the
+  // optional device-side row count (every kernel of this file, every epilogue): the launch is SIZED for M rows, the kernel computes *M_ptr <= M of them -- the
   // rows of a batch whose tail length only the device knows (step.py: the hard negatives drawn as text queries)
   const int* M_ptr;
 };
@@ -244,7 +244,7 @@ __device__ __forceinline__ void tile128_out(const GemmP& p, f32x16 (&acc)[2][2],
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] += b[j];
         }
-        if (p.R) {
+        if (p.R && (EPI != EPI_F32_ATOMIC || blockIdx.z == 0)) {      // like the bias: once, by the first K-slice of a split
           const bf16x4 r = *(const bf16x4*)(p.R + (long)m * p.ldr + n);
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] += (float)r[j];
@@ -1420,6 +1420,8 @@ extern "C" int spmm_gemm_nt(const void* A, long lda, const void* W, long ldw, in
   SPMM_CHECK_SHAPE(ldc % 4 == 0, "spmm_gemm_nt: ldc must be a multiple of 4");
   SPMM_CHECK_SHAPE(!is_bf16_epi(epi) || (ldc % 8 == 0 && (!R || ldr % 8 == 0) && (!G || ldg % 8 == 0) && (!C2 || ldc2 % 8 == 0) && (uintptr_t)C % 16 == 0),
                    "spmm_gemm_nt: bf16 outputs need 16-B aligned rows (ldc/ldr/ldg/ldc2 multiples of 8)");
+  SPMM_CHECK_SHAPE(is_bf16_epi(epi) || !R || (ldr % 4 == 0 && (uintptr_t)R % 8 == 0),
+                   "spmm_gemm_nt: R of an fp32-output epilogue is read 4 columns at a time (ldr a multiple of 4, R 8-B aligned)");
   SPMM_CHECK_SHAPE(((uintptr_t)A % 16 == 0) && ((uintptr_t)W % 16 == 0), "spmm_gemm_nt: A/W must be 16-B aligned");
   SPMM_CHECK_SHAPE(epi >= EPI_BF16 && epi <= EPI_MUL, "spmm_gemm_nt: unknown epilogue %d", epi);
   if (splits < 1) splits = 1;

@@ -133,6 +133,38 @@ def test_row_kernel_entry_points_refuse_incomplete_calls(built, i):
     assert name in str(e.value).split("): ", 1)[1], "the message names its entry point: " + str(e.value)
 
 
+def _gemm_nt_args(M=256, N=256, K=128, splits=1, R=None, ldr=0, ldc=256, epi=2, colsum=None, kernel=0):
+    return (P_, K, P_, K, M, N, K, splits, None, None, 1.0, R, ldr, None, 0, P_, ldc, None, 0, epi, colsum, kernel, None, None)
+
+
+F32_, ATOMIC_, ACC_ = 2, 3, 5          # SPMM_EPI_F32 / _F32_ATOMIC / _F32_ACC
+GEMM_NT_REFUSED = (
+    [(_gemm_nt_args(epi=e, kernel=k), "8-phase kernel needs a bf16-output epilogue") for e in (F32_, ATOMIC_, ACC_) for k in (8, 9)]
+    + [(_gemm_nt_args(epi=e, kernel=3), "256x256 kernel has bf16-output epilogues only") for e in (F32_, ATOMIC_, ACC_)]
+    + [(_gemm_nt_args(epi=ATOMIC_, kernel=2), "256x128 kernel has no atomic epilogue"),
+       (_gemm_nt_args(epi=ATOMIC_, kernel=2, splits=2), "256x128 kernel has no atomic epilogue"),
+       (_gemm_nt_args(epi=F32_, kernel=2, splits=2), "split-K needs the atomic epilogue"),
+       (_gemm_nt_args(epi=0, kernel=2, splits=2), "split-K needs the atomic epilogue")]
+    + [(_gemm_nt_args(epi=e, splits=2, kernel=k), "split-K needs the atomic epilogue") for e in (F32_, ACC_) for k in (0, 1, 5)]
+    + [(_gemm_nt_args(epi=e, N=258, ldc=260), "N=258 must be a multiple of 4") for e in (F32_, ATOMIC_, ACC_)]
+    + [(_gemm_nt_args(epi=e, ldc=258), "ldc must be a multiple of 4") for e in (F32_, ATOMIC_, ACC_)]
+    + [(_gemm_nt_args(epi=e, colsum=P_), "colsum is only fused into the bf16") for e in (F32_, ATOMIC_, ACC_)]
+    + [(_gemm_nt_args(epi=e, R=P_, ldr=258), "R of an fp32-output epilogue is read 4 columns at a time") for e in (F32_, ATOMIC_, ACC_)]
+    + [(_gemm_nt_args(epi=F32_, R=P_ + 4, ldr=256), "R of an fp32-output epilogue is read 4 columns at a time")])
+
+
+@pytest.mark.parametrize("i", range(len(GEMM_NT_REFUSED)))
+def test_gemm_nt_refuses_what_its_fp32_epilogues_do_not_support(built, i):
+    """spmm_gemm_nt with an fp32-output epilogue on a kernel that has none (8-phase, 256x256; the 256x128 kernel has no atomic one), split-K
+    without the atomic epilogue or on the 256x128 kernel, N or ldc that break the 16-byte stores, fused column sums, an R whose rows are not
+    8-byte aligned: each a SHAPE error (rc = 1) before any launch -- the pointers are dummies."""
+    from spmm_amd._lib import lib
+    args, msg = GEMM_NT_REFUSED[i]
+    with pytest.raises(RuntimeError, match=msg) as e:
+        lib().call("spmm_gemm_nt", *args)
+    assert "spmm_gemm_nt failed (rc=1)" in str(e.value) and "launch failed" not in str(e.value), str(e.value)
+
+
 def test_product_refuses_to_run_without_the_extension(tmp_path):
     """No CPU / eager fallback: with the shared library missing the library handle and the ops that reach it raise and name the file
     they looked for (ops that take a stream fail even earlier on a box without a GPU: torch reports the missing device)."""
