@@ -248,6 +248,26 @@ int spmm_beam_step_sampled(const float* logits, long ldl, int N, int k, int V, i
 int spmm_gumbel_noise(const uint64_t* seed_ptr, uint64_t salt, int N, int k, int V, int Lmax, int t, const int* t_ptr, int t_off,
                       const int* mol, long mol_base, float* out, long ldo, spmm_stream_t stream);
 
+/* Prefill of the decoder's self-attention cache (csrc/prefill.hip): the keys and values of E whole prefixes, computed by one packed pass,
+ * moved into the head-major caches of spmm_decode_attn -- keys and values of a layer in ONE launch.
+ * Source: K, V bf16 token-major rows with row stride ld elements, head h at column h*64 -- the K and V column blocks of the fused Q|K|V
+ * projection output [src_rows, 3H] of packed rows, passed as pointers into it (ld = 3H); src_rows = the rows the source has.
+ * Destination: Kc, Vc bf16 [R, nH, Lmax, 64] contiguous (decode.CachedDecoder.kc[l] / vc[l]).
+ * row0, len, dst_row: device int32 [E].  For entry e, head h < nH and position j < min(len[e], Lmax):
+ *     Kc[dst_row[e], h, j, :] = K[row0[e] + j, h*64 : h*64 + 64],  and the same for V.
+ * Several entries may read the same source rows; entries that name the same dst_row must not overlap in position (the order of their
+ * stores is undefined).
+ * Safety, part of the contract: everything read from device memory is clamped or skipped -- a position with row0[e] + j outside
+ * [0, src_rows) is neither read nor written; an entry with dst_row[e] outside [0, R) is skipped; len[e] <= 0 writes nothing; positions at
+ * or beyond Lmax are never written.  No byte of the caches outside the named (row, head, position) cells is written and nothing outside the
+ * src_rows rows (nH*64 columns of each) is read.  A pure move: 16-byte loads and stores of the same bits, NaN payloads and -0 included.
+ * No LDS, no atomics; any two launches give the same bytes.
+ * Refused before a launch (rc = 1): a null K, V, Kc, Vc, row0, len or dst_row with E > 0; nH < 1 or nH*64 > ld; ld not a multiple of 8;
+ * K, V, Kc or Vc not 16-byte aligned (row0, len, dst_row: 4 bytes); Lmax outside [1, 256]; R < 1, E < 0, src_rows < 1.  E == 0 returns 0
+ * without a launch. */
+int spmm_kv_prefill(const void* K, const void* V, long ld, long src_rows, const int* row0, const int* len, const int* dst_row, int E,
+                    void* Kc, void* Vc, int R, int nH, int Lmax, spmm_stream_t stream);
+
 /* mode 0: BertEmbeddings.forward xbert.py:193-220 from token ids.  mode 1: the PV path -- property_embed Linear(1,H),
  * bernoulli mask blend with property_mask, property_cls prepend (SPMM_models.py:82-88) fused with BertEmbeddings
  * (inputs_embeds branch).  Sequence s reads PV source row s % src_mod.  mode 2: generic inputs_embeds branch of

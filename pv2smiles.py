@@ -4,6 +4,7 @@ stochastic k-beam search with k = 2, any subset of the 53 properties left unspec
   python pv2smiles.py --checkpoint ./Pretrain/checkpoint_SPMM.ckpt --vocab_filename ./vocab_bpe_300.txt --input p2s_input.csv \
                       --property_names property_name.txt --normalize normalize.pkl --n_generate 1000 --k 2 --seed 7
   python pv2smiles.py --synthetic --tiny --n_generate 8 --seed 1                          (no data files: seeded weights, PV and vocabulary)
+  python pv2smiles.py ... --prefix c1ccccc1                                               (every molecule starts with this SMILES fragment)
 
 What differs from the reference, on purpose: the seed is a flag (the reference draws one at random) and the same seed gives the same
 molecules whatever `--chunk` is; all samples of a chunk are decoded together against a K/V cache (spmm_amd.decode.generate_with_property);
@@ -61,6 +62,18 @@ def synthetic_vocab(size: int):
     atoms = ["C", "c", "N", "n", "O", "o", "S", "s", "F", "Cl", "Br", "(", ")", "=", "#", "1", "2", "3", "4", "[nH]"]
     pieces = ["##" + a for a in atoms] + ["##" + a + b for a in atoms for b in atoms]
     return ["[PAD]", "[UNK]", "[CLS]", "[SEP]"] + pieces[: size - 4]
+
+
+def prefix_ids(tokenizer, fragment: str):
+    """--prefix: the SMILES fragment every molecule starts with -> token ids [CLS] piece_1 .. piece_n, tokenised as the model's text is
+    ('[CLS]' + fragment is one word: the literal [CLS] piece, then the fragment's pieces in their '##' form).  The fragment is tokenised
+    greedily on its own, so its last piece may differ from how a whole molecule would split there."""
+    if not fragment or fragment != "".join(fragment.split()):
+        raise SystemExit(f"--prefix {fragment!r}: a SMILES fragment without white space is needed")
+    ids = tokenizer.encode("[CLS]" + fragment)[1:-1]
+    if tokenizer.unk_token_id in ids or ids[0] != tokenizer.cls_token_id:
+        raise SystemExit(f"--prefix {fragment!r}: the vocabulary cannot spell this fragment ([UNK])")
+    return ids
 
 
 # ------------------------------------------------------------------------------------------------------------------- metrics
@@ -148,13 +161,18 @@ def main(args):
     model.eval()
     pv = prop_input if norm is None or args.synthetic else (prop_input - norm[0]) / norm[1]
     print(f"PV-to-SMILES generation in {'stochastic' if args.stochastic else 'deterministic'} manner with k={args.k}, seed {args.seed}...")
+    prefix = prefix_ids(tokenizer, args.prefix) if args.prefix else None
+    if prefix is not None:
+        print(f"prefix: {args.prefix!r} ({len(prefix)} tokens with [CLS]); every molecule starts with it")
     samples = decode.generate_with_property(model, pv.to(device), args.n_generate, prop_mask.to(device), k=args.k, stochastic=args.stochastic,
-                                            seed=args.seed, max_steps=args.max_steps, chunk=args.chunk or None)
+                                            seed=args.seed, max_steps=args.max_steps, chunk=args.chunk or None, prefix=prefix)
     smiles = [tokenizer.decode(s) for s in samples]
     with open(args.output, "w") as f:
         for s in smiles:
             f.write(s + "\n")
     print("=" * 50)
+    if prefix is not None:
+        print(f"prefix: {args.prefix} ({len(prefix)} tokens)")
     report(samples, smiles, prop_input, prop_mask, norm, names)
     print(f"Generated molecules are saved in '{args.output}'")
     print("=" * 50)
@@ -178,6 +196,7 @@ def parse_args(argv=None):
     p.add_argument("--output", default="generated_molecules.txt")
     p.add_argument("--max_steps", default=100, type=int, help="positions decoded at most")
     p.add_argument("--chunk", default=0, type=int, help="samples decoded together (0: all)")
+    p.add_argument("--prefix", default="", help="SMILES fragment every generated molecule starts with (tokenised as '[CLS]' + fragment)")
     p.add_argument("--synthetic", action="store_true", help="no data files: seeded weights, property vector and vocabulary")
     p.add_argument("--tiny", action="store_true", help="2-layer / 128-d encoders (configs/config_bert_tiny.json)")
     return p.parse_args(argv)

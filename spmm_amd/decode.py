@@ -17,11 +17,11 @@ CLS_ID, SEP_ID = 2, 3           # vocab_bpe_300.txt:3-4
 GRAPH_BELOW_ROWS = 200          # measured break-even of graph=True, not a switch (replay is opt-in): with the bookkeeping in one launch a position is a
 #                                 chain of ~130 dependent kernels (1.95 ms at 100 rows, 2.2 at 1 000, 3.6 at 5 000) and replay gains 7 % at 100 rows, 2 % at
 #                                 250, nothing from 500 on -- and a replayed graph has a fixed batch: no compaction of finished molecules
-last_run: dict = {}             # what the last eager beam_search_batched did: molecules, compactions, final_batch, positions
+last_run: dict = {}             # what the last eager beam_search_batched did: molecules, compactions, final_batch, positions, prefix_tokens, prefill
 COMPACT_BELOW = 0.75            # the batch is re-gathered once at most this share of its molecules is still live
 FUSED_BEAM_STEP = True          # beam bookkeeping of a position as one HIP launch (spmm_beam_step); False: the tensor-op form (BeamBook.update)
 GUMBEL_SALT = 0x50563253        # call-site salt of the sampled search's noise ("PV2S"; dropout and negative sampling use small integers)
-last_generate: dict = {}        # what the last generate_with_property did: samples, no_final, chunks
+last_generate: dict = {}        # what the last generate_with_property did: samples, no_final, chunks, prefix_tokens
 
 
 def _pick(p: torch.Tensor, k: int, stochastic: bool, generator=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -138,8 +138,12 @@ class BeamBook:
     k*k candidates survive.  need (None: k): the number of finals that stops a molecule -- `evaluate_beam` of reaction prediction
     (d_rxn_prediction.py:86-123) searches on until k*k hypotheses have ended; `results` returns the k best either way."""
 
-    def __init__(self, N: int, k: int, max_steps: int, device, fused: bool = False, need: int | None = None):
-        self.N, self.k, self.Lmax = N, k, max_steps + 3
+    def __init__(self, N: int, k: int, max_steps: int, device, fused: bool = False, need: int | None = None, prefix: torch.Tensor | None = None):
+        """prefix (int [N, P], P >= 1, prefix[:, 0] = [CLS]): every beam of molecule n starts from prefix[n] instead of [CLS] alone; the
+        search then generates up to max_steps + 1 further tokens.  Scores count the generated tokens only, finals carry the prefix."""
+        P = 1 if prefix is None else int(prefix.shape[1])
+        self.P = P
+        self.N, self.k, self.Lmax = N, k, P + max_steps + 2
         self.need = k if need is None else int(need)
         if not k <= self.need <= k * k:
             raise ValueError(f"need={need} outside [k, k*k] = [{k}, {k * k}]")
@@ -147,8 +151,11 @@ class BeamBook:
         it = torch.int32 if fused else torch.long         # fused: the state csrc/decode.hip::beam_step_kernel updates in place
         self.fused = fused
         self.tokens = torch.zeros(N, k, self.Lmax, dtype=it, device=device)
-        self.tokens[:, :, 0] = CLS_ID
-        self.t = 1                                        # tokens held by every live beam
+        if prefix is None:
+            self.tokens[:, :, 0] = CLS_ID
+        else:
+            self.tokens[:, :, :P] = prefix.to(device).to(it)[:, None, :]
+        self.t = P                                        # tokens held by every live beam
         self.cur_p = torch.zeros(N, k, device=device)
         self.fin_p = torch.full((N, self.F + 1), -float("inf"), device=device)           # slot F is a write-only dump
         self.fin_len = torch.zeros(N, self.F + 1, dtype=it, device=device)
@@ -159,10 +166,10 @@ class BeamBook:
         self.mol = None                                   # fused, after compact(): int32 indices of the molecules still decoded
 
     def first(self, values: torch.Tensor, indices: torch.Tensor):
-        """values/indices [N,k]: log-probs and ids of the k best successors of [CLS]."""
-        self.tokens[:, :, 1] = indices
+        """values/indices [N,k]: log-probs and ids of the k best successors of [CLS] (of the prefix: the token at position P)."""
+        self.tokens[:, :, self.P] = indices
         self.cur_p = values.clone()
-        self.t = 2
+        self.t = self.P + 1
 
     def update(self, values: torch.Tensor, indices: torch.Tensor, t: torch.Tensor | None = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """values/indices [N,k,k]: per live beam the k best next tokens.  Returns (parent [N,k], token [N,k]) of the new beams.
@@ -238,6 +245,22 @@ class BeamBook:
         return out
 
 
+def _prefix_rows(prefix_ids: torch.Tensor, pair_of_molecule, N: int, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The bookkeeping of a prefill on the host: pair_of_molecule [N] names the (condition, prefix) pair every molecule starts from ->
+    (it as int64 [N], dst int32 [Npairs]: the row that holds pair p's prefix = beam 0's row of the first molecule that starts from it)."""
+    if prefix_ids.dim() != 2 or prefix_ids.shape[0] < 1 or prefix_ids.shape[1] < 1:
+        raise ValueError(f"prefill: prefix_ids must be [Npairs, P] with P >= 1, got {tuple(prefix_ids.shape)}")
+    pom = torch.as_tensor(pair_of_molecule).detach().cpu().to(torch.int64).reshape(-1)
+    n_pairs = prefix_ids.shape[0]
+    if pom.numel() != N or int(pom.min()) < 0 or int(pom.max()) >= n_pairs:
+        raise ValueError(f"prefill: pair_of_molecule must name one of the {n_pairs} pairs for each of the {N} molecules")
+    first = torch.full((n_pairs,), N, dtype=torch.int64)
+    first.scatter_reduce_(0, pom, torch.arange(N, dtype=torch.int64), reduce="amin")
+    if int(first.max()) >= N:
+        raise ValueError("prefill: every pair must be the start of at least one molecule")
+    return pom, (first * k).to(torch.int32)
+
+
 class RecomputeDecoder:
     """Step function with the reference's cost model: re-runs the whole prefix of every beam through the module API
     (`model.text_encoder(..., is_decoder=True, return_logits=True)`), so it works with the CPU oracle as well."""
@@ -254,6 +277,15 @@ class RecomputeDecoder:
         return self.m.text_encoder(text, attention_mask=torch.ones_like(text), encoder_hidden_states=self.kv,
                                    encoder_attention_mask=torch.ones(self.kv.shape[:-1], dtype=torch.long, device=self.device),
                                    return_dict=True, is_decoder=True, return_logits=True)[:, -1, :]
+
+    def prefill(self, prefix_ids: torch.Tensor, pair_of_molecule, by_steps: bool = False) -> torch.Tensor:
+        """CachedDecoder.prefill for the whole-prefix forward: the rows are seeded with their prefix tokens -> logits [Npairs, V] for
+        position P (one forward over all rows; by_steps means nothing here)."""
+        pom, dst = _prefix_rows(prefix_ids, pair_of_molecule, self.tok.shape[0] // self.k, self.k)
+        rows = prefix_ids.to(self.device).long()[pom.to(self.device)].repeat_interleave(self.k, dim=0)        # [N*k, P]
+        P = rows.shape[1]
+        self.tok[:, :P - 1] = rows[:, :P - 1]
+        return self.step(rows[:, P - 1], P - 1)[dst.to(self.device).long()]
 
     def reorder(self, parent: torch.Tensor, t: int):
         N, k = parent.shape
@@ -305,6 +337,7 @@ class CachedDecoder:
         self.rows = torch.arange(self.R, dtype=torch.int32, device=dev)
         self.cols = torch.arange(Lmax, device=dev)
         self.rowmap = None                               # after compact(): cache row of every beam row still decoded (None: the row itself)
+        self.cond, self.repeat = prop_embeds, repeat     # (prefill: the conditions the fusion layers of the packed pass are bound to)
         if memory is not None:
             self.xkv_once = self.xkv = memory["xkv"]
             return
@@ -373,6 +406,62 @@ class CachedDecoder:
         return logits
 
     @torch.no_grad()
+    def prefill(self, prefix_ids: torch.Tensor, pair_of_molecule, by_steps: bool = False) -> torch.Tensor:
+        """Start every molecule from a prefix instead of [CLS] alone: prefix_ids int [Npairs, P] (position 0 = [CLS]), one row per
+        (condition, prefix) pair; pair_of_molecule [N] names the pair molecule n starts from, and the pair's condition is that molecule's
+        (one pair per molecule, or -- repeat > 1, many samples of one PV -- one pair for all).  -> fp32 logits [Npairs, V] for position P;
+        afterwards `step(ids, P)` continues.  Call it on a fresh decoder (before any step / compact).
+        One packed pass over the P positions of every pair, as score._decode_scores runs it (eval mode, no tape): the unimodal layers once
+        per DISTINCT prefix, the fusion layers per pair, each bound to its condition's keys | values (`xkv_once`: nothing is projected
+        again); every layer's self-attention K | V go from the Q|K|V projection into ONE cache row per pair (ops.kv_prefill), beam 0's
+        row of the first molecule that starts from the pair, and `anc[:, :P]` of every row names that row: the cache is never copied per
+        beam, and positions that all beams of a molecule read from one row are the attention kernel's shared-key fast path.  The LM head
+        runs on the pairs' last-position rows only.
+        by_steps=True: the twin on existing kernels only -- the prefix fed through `step` position by position on all N*k rows, identity
+        ancestry: the parity yard-stick and the timing baseline, not meant to be fast."""
+        from .engine import BF, KVSource, Group, Batch
+        if self.mem is not None:
+            raise ValueError("prefill: prompted decoding is for the PV decoder; a decoder with memory= (reaction prediction) has none")
+        eng, c, k, H, dev = self.eng, self.c, self.k, self.H, self.device
+        pom, dst = _prefix_rows(prefix_ids, pair_of_molecule, self.N, k)
+        n_pairs, P = prefix_ids.shape
+        if P >= self.Lmax:
+            raise ValueError(f"prefill: a prefix of {P} tokens does not fit a cache of Lmax={self.Lmax} positions")
+        ids_h = prefix_ids.detach().cpu().to(torch.int64)
+        if by_steps:
+            rows = ids_h[pom].repeat_interleave(k, dim=0).to(dev)               # [N*k, P]
+            for j in range(P):
+                logits = self.step(rows[:, j].contiguous(), j)
+            return logits[dst.to(dev).long()]
+        eng.train_mode = False
+        TP, f, n = self.pfx + "bert.", c.fusion_layer, c.num_hidden_layers
+        i32 = lambda a: a.to(torch.int32).contiguous().to(dev)                  # noqa: E731
+        uniq, inv = torch.unique(ids_h, dim=0, return_inverse=True)
+        U = uniq.shape[0]
+        dst_d, len_d = dst.to(dev), torch.full((n_pairs,), P, dtype=torch.int32, device=dev)
+        row0_lo, row0_hi = i32(inv * P), i32(torch.arange(n_pairs) * P)          # first source row of pair p: layers < f, layers >= f
+
+        def fill(row0, l, QKV):
+            ops.kv_prefill(QKV[:, H:2 * H], QKV[:, 2 * H:], row0, len_d, dst_d, self.kc[l], self.vc[l])
+
+        # ---- the unimodal layers, causal, once per distinct prefix (equal lengths: the dense rows are the packed rows)
+        x, _ = eng.embed_text(TP, c, i32(uniq), U, P, False)
+        text, _, _ = eng.stack_fwd(TP, c, range(0, f), False, x, Batch([Group(0, U, P, None, 0)]), False, kv_tap=functools.partial(fill, row0_lo))
+        # ---- the fusion layers: the pairs' query rows, causal, pair p bound to the condition of its first molecule
+        if U != n_pairs or not torch.equal(inv, torch.arange(n_pairs)):
+            text = text.index_select(0, (inv[:, None] * P + torch.arange(P)[None, :]).reshape(-1).to(dev))
+        Lp = self.Lp
+        proj = {f"{TP}encoder.layer.{l}.crossattention": KV for l, KV in self.xkv_once.items()}
+        cond = self.cond.to(dev).to(BF).reshape(-1, H).contiguous()
+        src = KVSource(cond, cond.shape[0] // Lp, Lp, proj=proj)
+        g = Batch([Group(0, n_pairs, P, None, 0).bind(src, i32((dst.long() // k) // self.repeat), 0)])
+        y, _, _ = eng.stack_fwd(TP, c, range(f, n), True, text, g, False, kv_tap=functools.partial(fill, row0_hi))
+        self.anc[:, :P] = dst_d[pom.to(dev)].repeat_interleave(k)[:, None]
+        last = y.index_select(0, (torch.arange(n_pairs) * P + P - 1).to(dev))
+        logits, _ = eng.lm_head_fwd(self.pfx, c, last, False)
+        return logits
+
+    @torch.no_grad()
     def reorder(self, parent: torch.Tensor, t):
         """New beam b of molecule n continues old beam parent[n, b]; positions < t are inherited, position t and everything behind it
         is its own.  t: int, or int64 [1] in device memory (graph replay).  The table is updated in place: its address is static."""
@@ -381,11 +470,54 @@ class CachedDecoder:
         torch.where(self.cols >= t, self.rows[:, None], anc, out=self.anc)
 
 
+PAD_ID = 0
+DECODE_MAXL = 256               # positions the decode kernels hold (spmm_decode_attn, spmm_beam_step, spmm_gumbel_noise)
+
+
+def check_prefix(prefix, N: int, vocab_size: int | None, max_steps: int) -> torch.Tensor | None:
+    """The `prefix` argument of the searches -> int64 [N or 1, P] on the host, or None for no prefix / [CLS] alone (today's start).
+    prefix: ints, [P] (one prefix for all molecules) or [N, P]; one length per call."""
+    if prefix is None:
+        return None
+    if not torch.is_tensor(prefix):
+        rows = list(prefix)
+        nested = [isinstance(r, (list, tuple)) or (torch.is_tensor(r) and r.dim() > 0) for r in rows]
+        if any(nested):
+            if not all(nested) or len({len(r) for r in rows}) != 1:
+                raise ValueError("prefix: prefixes of different lengths in one call; group the molecules by prefix length and call once per length")
+            rows = [[int(t) for t in r] for r in rows]
+        prefix = torch.tensor(rows, dtype=torch.int64)
+    if prefix.dtype.is_floating_point or prefix.dtype == torch.bool:
+        raise ValueError(f"prefix: token ids must be integers, got {prefix.dtype}")
+    p = prefix.detach().cpu().to(torch.int64)
+    if p.dim() == 1:
+        p = p[None, :]
+    elif p.dim() != 2:
+        raise ValueError(f"prefix: [P] or [N, P] token ids, got {p.dim()} dimensions")
+    if p.shape[1] < 1 or p.shape[0] not in (1, N):
+        raise ValueError(f"prefix: shape {tuple(p.shape)} is neither [P] nor [N, P] with N = {N} molecules and P >= 1")
+    if bool((p[:, 0] != CLS_ID).any()):
+        raise ValueError(f"prefix: the first token must be [CLS] ({CLS_ID})")
+    if bool(((p == SEP_ID) | (p == PAD_ID)).any()):
+        raise ValueError(f"prefix: [SEP] ({SEP_ID}) or PAD ({PAD_ID}) inside a prefix")
+    if int(p.min()) < 0 or (vocab_size is not None and int(p.max()) >= vocab_size):
+        raise ValueError(f"prefix: token id {int(p.max()) if int(p.min()) >= 0 else int(p.min())} outside the vocabulary of {vocab_size}")
+    P = p.shape[1]
+    if P + max_steps + 2 > DECODE_MAXL:
+        raise ValueError(f"prefix: P + max_steps + 2 = {P} + {max_steps} + 2 = {P + max_steps + 2} positions exceed the {DECODE_MAXL} the decode "
+                         "kernels hold (max_steps counts positions after the prefix)")
+    return None if P == 1 else p
+
+
+def _vocab_size(model) -> int | None:
+    return getattr(getattr(getattr(model, "cfg", None), "text", None), "vocab_size", None)
+
+
 @torch.no_grad()
 def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int = 100, cached: bool | None = None,
                         sync_every: int = 4, prop_mask: torch.Tensor | None = None, stochastic: bool = False,
                         generator=None, graph: bool | None = None, compact: bool = True, seed: int | None = None,
-                        mol_base: int = 0) -> List[List[Tuple[float, List[int]]]]:
+                        mol_base: int = 0, prefix=None, prefill: bool = True) -> List[List[Tuple[float, List[int]]]]:
     """The reference's beam search for N molecules at once (props [N,53]); result[n] is what the one-molecule search
     (oracle/decode_oracle.py::beam_search) returns for props[n].
     cached=True (default on the HIP model) decodes one token per step against the K/V cache; cached=False re-runs the prefix
@@ -402,15 +534,28 @@ def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int =
     capture is process-global on the capture stream's device -- another thread touching the GPU meanwhile aborts it -- and a replayed
     graph cannot drop finished molecules; it gains 7 % at 100 beam rows and nothing from 500 on (GRAPH_BELOW_ROWS).  A sampled search
     (seeded or not) stays eager whatever `graph` says.  compact=True (eager fused path): finished
-    molecules are dropped from the batch as the search goes (same results; the reference decodes one molecule at a time and simply stops)."""
+    molecules are dropped from the batch as the search goes (same results; the reference decodes one molecule at a time and simply stops).
+    prefix: the beginning of every molecule -- token ids [P] (one prefix for all molecules) or [N, P], a list or a tensor, starting with
+    [CLS], no [SEP] or PAD inside, one length per call (ValueError otherwise: the caller groups molecules by prefix length).  Every
+    hypothesis then starts with its prefix, its score counts the generated tokens only, and max_steps counts positions after the prefix
+    (P + max_steps + 2 <= 256).  The noise of a seeded search is keyed by the absolute position, so the first pick draws at P - 1.
+    prefill=True: the prefix goes through the decoder once, in one packed pass, into one cache row per molecule that all its beams read
+    (CachedDecoder.prefill); prefill=False: it is stepped through position by position on every beam row (the twin on the existing
+    kernels).  cached=False seeds the whole-prefix forward with the tokens.  A search with a prefix stays eager whatever `graph` says.
+    prefix=None, or [CLS] alone, is the search without a prefix, unchanged."""
     if cached is None:
         cached = hasattr(model, "engine")
+    prefix = check_prefix(prefix, props.shape[0], _vocab_size(model), max_steps)
     prop_embeds = encode_properties(model, props, prop_mask)
     if cached:
         model.engine.train_mode = False
-    dec = (CachedDecoder if cached else RecomputeDecoder)(model, prop_embeds, k, max_steps + 3)
-    return _search(model, dec, prop_embeds.shape[0], k=k, max_steps=max_steps, sync_every=sync_every, stochastic=stochastic, generator=generator,
-                   graph=bool(graph), compact=compact, seed=seed, mol_base=mol_base)
+    N = prop_embeds.shape[0]
+    P = 1 if prefix is None else prefix.shape[1]
+    dec = (CachedDecoder if cached else RecomputeDecoder)(model, prop_embeds, k, P + max_steps + 2)
+    if prefix is not None:
+        prefix = prefix.expand(N, P)                     # one (PV, prefix) pair per molecule; equal prefixes share the unimodal layers
+    return _search(model, dec, N, k=k, max_steps=max_steps, sync_every=sync_every, stochastic=stochastic, generator=generator,
+                   graph=bool(graph), compact=compact, seed=seed, mol_base=mol_base, prefix=prefix, pair_of_molecule=range(N), prefill=prefill)
 
 
 def _advance(dec, book: BeamBook, ids: torch.Tensor, t: int, *, t_dev: torch.Tensor | None = None, noise=None, pick=None,
@@ -434,33 +579,44 @@ def _advance(dec, book: BeamBook, ids: torch.Tensor, t: int, *, t_dev: torch.Ten
 
 
 def _search(model, dec, N: int, *, k: int, max_steps: int, sync_every: int = 4, stochastic: bool = False, generator=None, graph: bool = False,
-            compact: bool = True, seed: int | None = None, mol_base: int = 0, need: int | None = None):
+            compact: bool = True, seed: int | None = None, mol_base: int = 0, need: int | None = None, prefix: torch.Tensor | None = None,
+            pair_of_molecule=None, prefill: bool = True):
     """beam_search_batched behind the decoder's construction (generate_with_property builds its decoders from one encoded PV).
-    need: finals that end a molecule's search (BeamBook; None: k)."""
+    need: finals that end a molecule's search (BeamBook; None: k).  prefix (check_prefix's result, int64 [Npairs, P], P >= 2) with
+    pair_of_molecule [N]: molecule n starts from prefix[pair_of_molecule[n]] (CachedDecoder.prefill; prefill=False: its stepping twin);
+    the decoder was built for Lmax = P + max_steps + 2."""
     last_run.clear()
     cached, dev = isinstance(dec, CachedDecoder), dec.device
-    ids = torch.full((N * k,), CLS_ID, dtype=torch.long, device=dev)
-    logits = dec.step(ids, 0).view(N, k, -1)[:, 0].float()              # all k rows hold the same [CLS] prefix
-    Lmax, V = max_steps + 3, logits.shape[-1]
+    P = 1 if prefix is None else int(prefix.shape[1])
+    if prefix is not None and P + max_steps + 2 > DECODE_MAXL:
+        raise ValueError(f"P + max_steps + 2 = {P} + {max_steps} + 2 exceeds the {DECODE_MAXL} positions the decode kernels hold")
+    if prefix is None:
+        ids = torch.full((N * k,), CLS_ID, dtype=torch.long, device=dev)
+        logits = dec.step(ids, 0).view(N, k, -1)[:, 0].float()              # all k rows hold the same [CLS] prefix
+    else:
+        pom = torch.as_tensor(pair_of_molecule).to(torch.int64)
+        logits = dec.prefill(prefix, pom, by_steps=not prefill)[pom.to(dev)].float()      # [N, V]: the k rows of a molecule hold the same prefix
+        prefix = prefix[pom]
+    Lmax, V = P + max_steps + 2, logits.shape[-1]
     seeded = bool(stochastic and seed is not None)
     # one launch per position for the beam bookkeeping (csrc/decode.hip::beam_step_kernel: k <= 8 beams, vocabulary <= 512, histories <= 256
     # tokens -- the tensor-op bookkeeping serves everything else); spmm_gumbel_noise accepts the same shapes
     fits = bool(cached and k <= 8 and model.cfg.text.vocab_size <= 512 and Lmax <= 256)
-    book = BeamBook(N, k, max_steps, dev, fused=bool(fits and FUSED_BEAM_STEP and (seeded or not stochastic)), need=need)
+    book = BeamBook(N, k, max_steps, dev, fused=bool(fits and FUSED_BEAM_STEP and (seeded or not stochastic)), need=need, prefix=prefix)
     noise_at = _GumbelNoise(seed, mol_base, N, k, V, Lmax, dev, on_device=fits) if seeded else None
 
     def pick(logits, noise):
         return _pick_seeded(logits, noise, k) if seeded else _pick(torch.softmax(logits, dim=-1), k, stochastic, generator)
 
-    values, indices = pick(logits, noise_at(0).view(N, k, -1)[:, 0] if seeded else None)
+    values, indices = pick(logits, noise_at(P - 1).view(N, k, -1)[:, 0] if seeded else None)      # (noise keyed by the absolute position)
     book.first(values, indices)
     ids = indices.reshape(N * k)
-    if graph and cached and not stochastic:
+    if graph and cached and not stochastic and prefix is None:
         return _decode_graphed(dec, book, ids, max_steps, sync_every)
     n_cur = N
-    last_run.update(molecules=N, compactions=0, final_batch=N, positions=0)
+    last_run.update(molecules=N, compactions=0, final_batch=N, positions=0, prefix_tokens=P, prefill=bool(prefix is not None and prefill))
     for s in range(max_steps):
-        ids = _advance(dec, book, ids, s + 1, noise=noise_at, pick=pick)
+        ids = _advance(dec, book, ids, P + s, noise=noise_at, pick=pick)
         last_run["positions"] = s + 1
         if s % sync_every != sync_every - 1:
             continue
@@ -486,15 +642,21 @@ def _search(model, dec, N: int, *, k: int, max_steps: int, sync_every: int = 4, 
 
 @torch.no_grad()
 def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: torch.Tensor | None = None, k: int = 2, stochastic: bool = True,
-                           seed: int = 0, max_steps: int = 100, chunk: int | None = None) -> List[List[int]]:
+                           seed: int = 0, max_steps: int = 100, chunk: int | None = None, prefix=None, prefill: bool = True) -> List[List[int]]:
     """`generate_with_property` of d_pv2smiles_single.py:54-111: n_sample molecules from ONE (normalised) property vector pv [53], with the
     properties of prop_mask ([53], 1 = unspecified) replaced by the mask token.  Returns one token-id list per sample ([CLS] ... [SEP]; empty
     when the search of that sample finished nothing -- counted in last_generate["no_final"]).
     The PV is encoded once, on one row; the cross-attention keys / values are projected once per fusion layer and copied for the samples of
     a chunk (`chunk` samples are decoded together; None: all of them).  Sample i is molecule i of the seeded search (beam_search_batched(seed=...,
     mol_base=...)), so the samples do not depend on the chunking.  As in the reference (:102-110) a stochastic run returns one of each sample's
-    up-to-k finals, picked by random.Random(seed) on the host in sample order; a deterministic run returns the best final."""
+    up-to-k finals, picked by random.Random(seed) on the host in sample order; a deterministic run returns the best final.
+    prefix (token ids [P], see beam_search_batched): every sample starts with it.  It is ONE (PV, prefix) pair: each chunk runs it
+    through the decoder once into cache row 0, which every beam row of every sample of the chunk reads (prefill=False: stepped through on
+    every row).  The samples still do not depend on the chunking: the noise is keyed by the absolute position.
+    last_generate["prefix_tokens"] = P (1 without a prefix)."""
     cached = hasattr(model, "engine")
+    prefix = check_prefix(prefix, 1, _vocab_size(model), max_steps)
+    P = 1 if prefix is None else prefix.shape[1]
     prop_embeds = encode_properties(model, pv.reshape(1, -1), None if prop_mask is None else prop_mask.reshape(1, -1))
     if cached:
         model.engine.train_mode = False
@@ -505,11 +667,12 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
     for base in range(0, n_sample, chunk):
         n = min(chunk, n_sample - base)
         if cached:
-            dec = CachedDecoder(model, prop_embeds, k, max_steps + 3, repeat=n, xkv=xkv)
+            dec = CachedDecoder(model, prop_embeds, k, P + max_steps + 2, repeat=n, xkv=xkv)
             xkv = dec.xkv_once
         else:
-            dec = RecomputeDecoder(model, prop_embeds.expand(n, -1, -1), k, max_steps + 3)
-        res = _search(model, dec, n, k=k, max_steps=max_steps, stochastic=stochastic, seed=seed if stochastic else None, mol_base=base)
+            dec = RecomputeDecoder(model, prop_embeds.expand(n, -1, -1), k, P + max_steps + 2)
+        res = _search(model, dec, n, k=k, max_steps=max_steps, stochastic=stochastic, seed=seed if stochastic else None, mol_base=base,
+                      prefix=prefix, pair_of_molecule=[0] * n, prefill=prefill)
         for finals in res:
             if not finals:
                 none += 1
@@ -517,7 +680,7 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
             else:
                 out.append(finals[rng.randrange(len(finals)) if stochastic else 0][1])
     last_generate.clear()
-    last_generate.update(samples=n_sample, no_final=none, chunks=(n_sample + chunk - 1) // chunk)
+    last_generate.update(samples=n_sample, no_final=none, chunks=(n_sample + chunk - 1) // chunk, prefix_tokens=P)
     return out
 
 

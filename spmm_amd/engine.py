@@ -423,8 +423,9 @@ class Engine:
         self._wgrad(dx, A, P.g(op + "dense.weight"), md=md)
         return dz, dx
 
-    def _attn_block_fwd(self, pfx, c, X, groups, save, cross, X32=None):
+    def _attn_block_fwd(self, pfx, c, X, groups, save, cross, X32=None, kv_tap=None):
         """BertAttention.forward xbert.py:401-422 on a token batch.  cross=True uses the groups' key/value sources.
+        kv_tap (self-attention only): called with the fused Q|K|V projection [M, 3H] right after it is formed (`stack_fwd`).
         -> (y, tape entry, fp32 twin of y or None)."""
         P, H, nH = self.P, c.hidden_size, c.num_attention_heads
         # Every form of the block draws its salts here, in one order (every group's attention salt, then the hidden one): the composite of
@@ -433,7 +434,7 @@ class Engine:
         salt_h = self._next_salt()
         sv = {"X": X, "salt_a": salts_a, "cross": cross}
         if not cross:
-            ctx, core = self._self_attn_fwd(pfx, c, X, groups, save, salts_a)
+            ctx, core = self._self_attn_fwd(pfx, c, X, groups, save, salts_a, kv_tap)
         else:
             sv["Qc"] = Qc = ops.gemm_nt(X, P.wb(pfx + ".self.query.weight"), self._new(X.shape[0], H), bias=P.w(pfx + ".self.query.bias"),
                                         M_dev=groups.rows_dev)
@@ -468,12 +469,14 @@ class Engine:
         sv.update(core, ctx=ctx, ln=ln)
         return y, (sv if save else None), y32
 
-    def _self_attn_fwd(self, pfx, c, X, groups, save, salts):
+    def _self_attn_fwd(self, pfx, c, X, groups, save, salts, kv_tap=None):
         """Self-attention core: the fused Q/K/V projection of the batch, then one attention launch per group.  -> (ctx, tape fields)"""
         P, H, nH, M = self.P, c.hidden_size, c.num_attention_heads, X.shape[0]
         Wqkv = P.fused(pfx + ".self.", ("query", "key", "value"), "weight")
         bqkv = P.fused(pfx + ".self.", ("query", "key", "value"), "bias", what="w")
         QKV = ops.gemm_nt(X, Wqkv, self._new(M, 3 * H), bias=bqkv, M_dev=groups.rows_dev)
+        if kv_tap is not None:
+            kv_tap(QKV)
         ctx, lses = self._new(M, H), []
         skv = {}                                                 # K/V of the groups' private self-attention sources (SelfKV), one GEMM each
         for g, salt in zip(groups, salts):
@@ -626,10 +629,11 @@ class Engine:
         return dX
 
     # ------------------------------------------------------------------------------------------------- layers
-    def _layer_fwd(self, lp, c, has_cross, X, groups, save, X32=None):
+    def _layer_fwd(self, lp, c, has_cross, X, groups, save, X32=None, kv_tap=None):
         """BertLayer.forward xbert.py:469-534.  -> (y, tape entry, fp32 twin of y or None)."""
         P, H, I, M = self.P, c.hidden_size, c.intermediate_size, X.shape[0]
-        a, sv1, a32 = self._attn_block_fwd(lp + "attention", c, X, groups, save, cross=False, X32=X32)
+        tap = {} if kv_tap is None else {"kv_tap": kv_tap}       # (without a tap the call is the one it always was: bench.py wraps this method)
+        a, sv1, a32 = self._attn_block_fwd(lp + "attention", c, X, groups, save, cross=False, X32=X32, **tap)
         sv2 = None
         if has_cross:
             a, sv2, a32 = self._attn_block_fwd(lp + "crossattention", c, a, groups, save, cross=True, X32=a32)
@@ -657,12 +661,15 @@ class Engine:
             da = self._attn_block_bwd(lp + "crossattention", c, sv["cross"], da, groups, dkv_acc)
         return self._attn_block_bwd(lp + "attention", c, sv["att"], da, groups, None)
 
-    def stack_fwd(self, pfx, c, layers, has_cross, X, groups, save, X32=None):
+    def stack_fwd(self, pfx, c, layers, has_cross, X, groups, save, X32=None, kv_tap=None):
         """groups: the Batch X holds.  -> (y, tape, y32).  With X32 (the fp32 twin of X: EngineOptions.resid_fp32) the residual stream runs
-        in fp32 and y32 is the fp32 twin of y (None otherwise)."""
+        in fp32 and y32 is the fp32 twin of y (None otherwise).  kv_tap(layer index, QKV [M, 3H]) is called with every layer's
+        self-attention Q|K|V projection right after it is formed (decode.CachedDecoder.prefill fills its K/V cache from it); None, the
+        default, changes nothing -- no launch, no salt."""
         tape = []
         for i in layers:
-            X, sv, X32 = self._layer_fwd(f"{pfx}encoder.layer.{i}.", c, has_cross and i >= c.fusion_layer, X, groups, save, X32=X32)
+            tap = None if kv_tap is None else functools.partial(kv_tap, i)
+            X, sv, X32 = self._layer_fwd(f"{pfx}encoder.layer.{i}.", c, has_cross and i >= c.fusion_layer, X, groups, save, X32=X32, kv_tap=tap)
             tape.append(sv)
         return X, tape, X32
 

@@ -623,6 +623,21 @@ def gumbel_noise(seed, N, k, V, Lmax, *, salt=0, t=0, t_ptr=None, t_off=0, mol=N
     return out
 
 
+def kv_prefill(K, V, row0, length, dst_row, Kc, Vc):
+    """Whole prefixes into the decoder's self-attention cache (csrc/prefill.hip, spmm_kv_prefill): K / V bf16 [rows, nH*64] views of
+    token-major rows with one row stride (the K and V column blocks of a fused Q|K|V projection); Kc / Vc bf16 [R, nH, Lmax, 64]
+    contiguous; row0 / length / dst_row int32 [E] on the device.  Entry e: positions j < min(length[e], Lmax) of cache row dst_row[e] take
+    source rows row0[e] + j.  Keys and values in one launch; rows, lengths and destinations out of range are skipped, never clamped onto
+    other cells."""
+    R, nH, Lmax, dh = Kc.shape
+    assert K.dtype == BF16 and V.dtype == BF16 and Kc.dtype == BF16 and Vc.dtype == BF16 and dh == 64
+    assert K.shape == V.shape and K.shape[1] == nH * 64 and _row_stride(K) == _row_stride(V)
+    assert Kc.is_contiguous() and Vc.is_contiguous() and Vc.shape == Kc.shape
+    E = row0.numel()
+    assert all(t.dtype == torch.int32 and t.numel() == E and t.is_contiguous() and t.device == Kc.device for t in (row0, length, dst_row))
+    _call("spmm_kv_prefill", _p(K), _p(V), _row_stride(K), K.shape[0], _p(row0), _p(length), _p(dst_row), E, _p(Kc), _p(Vc), R, nH, Lmax, _st())
+
+
 def segment_sum_bf16(src, start, lst, out):
     """out[u] = sum_{k in [start[u], start[u+1])} src[list[k]] over rows of W bf16 elements (fp32 accumulation)."""
     U, W = out.shape
