@@ -248,6 +248,23 @@ int spmm_beam_step_sampled(const float* logits, long ldl, int N, int k, int V, i
 int spmm_gumbel_noise(const uint64_t* seed_ptr, uint64_t salt, int N, int k, int V, int Lmax, int t, const int* t_ptr, int t_off,
                       const int* mol, long mol_base, float* out, long ldo, spmm_stream_t stream);
 
+/* Logit warp in front of the beam step (csrc/warp.hip): guidance, temperature, top-k and nucleus truncation of the next-token logits of R
+ * beam rows, one launch.  lc, lu (may be null), out: fp32 rows of V logits, row strides ld (lc and lu) and ldo.  Per row:
+ *   1. g_j = lu_j + w * (lc_j - lu_j) (classifier-free guidance: lc the conditioned, lu the all-masked logits; raw logits suffice, the
+ *      per-row constants of the two log-softmaxes vanish in the next softmax); lu == null: g_j = lc_j exactly.
+ *   2. z_j = g_j / temperature; temperature == 1: z_j = g_j exactly.
+ *   3. Tokens are ranked by (z descending, j ascending): a tie goes to the lower index, as in spmm_beam_step.
+ *   4. K = top_k if 0 < top_k < V, else V; q = softmax of z over the K best-ranked tokens.  The token of rank r is kept iff r < min_keep,
+ *      or r < K and the sum of q over the ranks < r is < top_p.  top_p == 1 is "no nucleus cut": every partial sum of q is below 1.
+ *   5. out_j = z_j if kept, else -inf.
+ * min_keep is the search's k: the sampled beam step draws k tokens without replacement per row, so every row keeps >= k finite entries.
+ * The columns [V, ld) of the inputs and [V, ldo) of out are neither read nor written; out may be lc (a row is read whole before it is
+ * written).  fp32 throughout; every sum of a row has a fixed order, so a row's result does not depend on the rest of the launch.
+ * Refused before a launch (rc = 1): R < 0; min_keep outside [1, 8]; V outside [min_keep, 512]; ld or ldo < V; temperature <= 0 or not
+ * finite; top_p outside (0, 1]; top_k < 0; w not finite; with R > 0 a null lc or out.  R == 0 returns 0 without a launch. */
+int spmm_logit_warp(const float* lc, const float* lu, long ld, int R, int V, float w, float temperature, int top_k, float top_p,
+                    int min_keep, float* out, long ldo, spmm_stream_t stream);
+
 /* Prefill of the decoder's self-attention cache (csrc/prefill.hip): the keys and values of E whole prefixes, computed by one packed pass,
  * moved into the head-major caches of spmm_decode_attn -- keys and values of a layer in ONE launch.
  * Source: K, V bf16 token-major rows with row stride ld elements, head h at column h*64 -- the K and V column blocks of the fused Q|K|V

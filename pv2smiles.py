@@ -5,6 +5,13 @@ stochastic k-beam search with k = 2, any subset of the 53 properties left unspec
                       --property_names property_name.txt --normalize normalize.pkl --n_generate 1000 --k 2 --seed 7
   python pv2smiles.py --synthetic --tiny --n_generate 8 --seed 1                          (no data files: seeded weights, PV and vocabulary)
   python pv2smiles.py ... --prefix c1ccccc1                                               (every molecule starts with this SMILES fragment)
+  python pv2smiles.py ... --guidance 2 --temperature 0.8 --top_k 40 --top_p 0.95          (the distribution the samples are drawn from)
+
+--guidance w is classifier-free guidance between the requested condition and the same decoder with every property masked,
+log p~ = log p_u + w (log p_c - log p_u): 1 (default) is the conditioned model alone, w > 1 pushes the samples towards the requested
+properties, 0 is the unconditional model.  --temperature divides the guided logits, --top_k keeps the K most probable tokens (0: all; at
+least --k), --top_p the smallest set of them whose probability reaches p (1: all).  Order: guidance, temperature, top-k, then top-p on
+the renormalised distribution; at least --k tokens always stay.  With all four at their defaults the run is the one without them.
 
 What differs from the reference, on purpose: the seed is a flag (the reference draws one at random) and the same seed gives the same
 molecules whatever `--chunk` is; all samples of a chunk are decoded together against a K/V cache (spmm_amd.decode.generate_with_property);
@@ -114,6 +121,10 @@ def main(args):
     device = torch.device(args.device)
     torch.manual_seed(args.seed)
     from spmm_amd import decode
+    try:
+        warp = decode.check_warp(args.guidance, args.temperature, args.top_k, args.top_p, args.k)       # (before the model is built)
+    except ValueError as e:
+        raise SystemExit(f"pv2smiles.py: {e}")
     from spmm_amd.model import SPMM
     from spmm_amd.tokenizer import SmilesWordPiece
 
@@ -162,10 +173,13 @@ def main(args):
     pv = prop_input if norm is None or args.synthetic else (prop_input - norm[0]) / norm[1]
     print(f"PV-to-SMILES generation in {'stochastic' if args.stochastic else 'deterministic'} manner with k={args.k}, seed {args.seed}...")
     prefix = prefix_ids(tokenizer, args.prefix) if args.prefix else None
+    if warp is not None:
+        print(f"sampling: guidance {warp['guidance']:g}, temperature {warp['temperature']:g}, top_k {warp['top_k']}, top_p {warp['top_p']:g}")
     if prefix is not None:
         print(f"prefix: {args.prefix!r} ({len(prefix)} tokens with [CLS]); every molecule starts with it")
     samples = decode.generate_with_property(model, pv.to(device), args.n_generate, prop_mask.to(device), k=args.k, stochastic=args.stochastic,
-                                            seed=args.seed, max_steps=args.max_steps, chunk=args.chunk or None, prefix=prefix)
+                                            seed=args.seed, max_steps=args.max_steps, chunk=args.chunk or None, prefix=prefix,
+                                            guidance=args.guidance, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
     smiles = [tokenizer.decode(s) for s in samples]
     with open(args.output, "w") as f:
         for s in smiles:
@@ -197,6 +211,11 @@ def parse_args(argv=None):
     p.add_argument("--max_steps", default=100, type=int, help="positions decoded at most")
     p.add_argument("--chunk", default=0, type=int, help="samples decoded together (0: all)")
     p.add_argument("--prefix", default="", help="SMILES fragment every generated molecule starts with (tokenised as '[CLS]' + fragment)")
+    p.add_argument("--guidance", default=1.0, type=float, help="classifier-free guidance weight w between the condition and the all-masked PV: "
+                   "1 = the conditioned model alone (default), > 1 towards the requested properties, 0 = unconditional")
+    p.add_argument("--temperature", default=1.0, type=float, help="divides the (guided) logits; > 0")
+    p.add_argument("--top_k", default=0, type=int, help="keep the K most probable tokens (0: all; not below --k, which are always kept)")
+    p.add_argument("--top_p", default=1.0, type=float, help="nucleus: keep the most probable tokens until their probability reaches p, in (0, 1] (1: all)")
     p.add_argument("--synthetic", action="store_true", help="no data files: seeded weights, property vector and vocabulary")
     p.add_argument("--tiny", action="store_true", help="2-layer / 128-d encoders (configs/config_bert_tiny.json)")
     return p.parse_args(argv)

@@ -5,6 +5,7 @@ restated in oracle/decode_oracle.py -- test infrastructure, the yard-stick of te
 from __future__ import annotations
 
 import functools
+import math
 import random
 from typing import List, Tuple
 
@@ -17,11 +18,13 @@ CLS_ID, SEP_ID = 2, 3           # vocab_bpe_300.txt:3-4
 GRAPH_BELOW_ROWS = 200          # measured break-even of graph=True, not a switch (replay is opt-in): with the bookkeeping in one launch a position is a
 #                                 chain of ~130 dependent kernels (1.95 ms at 100 rows, 2.2 at 1 000, 3.6 at 5 000) and replay gains 7 % at 100 rows, 2 % at
 #                                 250, nothing from 500 on -- and a replayed graph has a fixed batch: no compaction of finished molecules
-last_run: dict = {}             # what the last eager beam_search_batched did: molecules, compactions, final_batch, positions, prefix_tokens, prefill
+last_run: dict = {}             # what the last eager beam_search_batched did: molecules, compactions, final_batch, positions, prefix_tokens, prefill,
+#                                 guidance, temperature, top_k, top_p, baseline_rows (0, or the N*k rows of the all-masked branch)
 COMPACT_BELOW = 0.75            # the batch is re-gathered once at most this share of its molecules is still live
 FUSED_BEAM_STEP = True          # beam bookkeeping of a position as one HIP launch (spmm_beam_step); False: the tensor-op form (BeamBook.update)
 GUMBEL_SALT = 0x50563253        # call-site salt of the sampled search's noise ("PV2S"; dropout and negative sampling use small integers)
-last_generate: dict = {}        # what the last generate_with_property did: samples, no_final, chunks, prefix_tokens
+last_generate: dict = {}        # what the last generate_with_property did: samples, no_final, chunks, prefix_tokens, guidance, temperature, top_k, top_p,
+#                                 baseline_rows (of the last chunk)
 
 
 def _pick(p: torch.Tensor, k: int, stochastic: bool, generator=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -100,6 +103,63 @@ def _pick_seeded(logits: torch.Tensor, noise: torch.Tensor, k: int) -> Tuple[tor
     instantiation of csrc/decode.hip::beam_step_kernel: both form the keys with the same single fp32 add."""
     ids = torch.topk(logits + noise.to(logits.dtype).reshape(logits.shape), k=k, dim=-1).indices
     return torch.log_softmax(logits, dim=-1).gather(-1, ids), ids
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The distribution the search draws from: guidance towards the condition, temperature, top-k and nucleus truncation.
+# ------------------------------------------------------------------------------------------------------------------
+def check_warp(guidance: float, temperature: float, top_k: int, top_p: float, k: int) -> dict | None:
+    """The four sampling controls of the searches -> None when all are at their defaults (the search is then today's, launch for launch),
+    else dict(guidance, temperature, top_k, top_p).  ValueError for temperature <= 0 or not finite, top_p outside (0, 1], top_k < 0 or not
+    an integer, a non-finite guidance, and an explicit top_k in [1, k): every beam draws k distinct tokens, so k are always kept
+    (min_keep) and a smaller request would be overridden silently."""
+    if isinstance(top_k, bool) or int(top_k) != top_k:
+        raise ValueError(f"top_k={top_k!r} must be an integer >= 0 (0: no top-k cut)")
+    guidance, temperature, top_k, top_p = float(guidance), float(temperature), int(top_k), float(top_p)
+    if not math.isfinite(guidance):
+        raise ValueError(f"guidance={guidance} must be finite (1: the conditioned model alone, 0: the all-masked baseline, > 1: towards the condition)")
+    if not (math.isfinite(temperature) and temperature > 0):
+        raise ValueError(f"temperature={temperature} must be finite and > 0")
+    if not 0 < top_p <= 1:
+        raise ValueError(f"top_p={top_p} outside (0, 1]")
+    if top_k < 0:
+        raise ValueError(f"top_k={top_k} must be >= 0 (0: no top-k cut)")
+    if 0 < top_k < k:
+        raise ValueError(f"top_k={top_k} is below the k={k} tokens every beam draws: k tokens are always kept, ask for top_k >= k (or 0)")
+    if guidance == 1.0 and temperature == 1.0 and top_k == 0 and top_p == 1.0:
+        return None
+    return dict(guidance=guidance, temperature=temperature, top_k=top_k, top_p=top_p)
+
+
+NO_WARP = dict(guidance=1.0, temperature=1.0, top_k=0, top_p=1.0)
+
+
+def warp_logits(lc: torch.Tensor, lu: torch.Tensor | None = None, *, guidance: float = 1.0, temperature: float = 1.0, top_k: int = 0,
+                top_p: float = 1.0, min_keep: int = 1) -> torch.Tensor:
+    """The rules of spmm_logit_warp (include/spmm_hip.h; csrc/warp.hip) as tensor ops, any device and dtype, over the last dimension:
+      1. g = lu + guidance * (lc - lu), the classifier-free contrast between the conditioned logits lc and the all-masked ones lu (raw
+         logits: the constants of the two log-softmaxes vanish in the next softmax); lu=None: g = lc;
+      2. z = g / temperature (temperature == 1: z = g);
+      3. tokens ranked by (z descending, index ascending);
+      4. K = top_k if 0 < top_k < V else V, q = softmax of z over the K best; rank r is kept iff r < min_keep, or r < K and the q-mass of
+         the ranks < r is < top_p (top_p == 1: no nucleus cut);
+      5. z where kept, -inf elsewhere.
+    The searches read the result as logits: the recorded log-probabilities are those of the warped distribution, renormalised over the
+    kept tokens.  The route of every search the one-launch beam step does not take, and the float64 reference of the kernel's tests.
+    With every argument at its default the input comes back as it is."""
+    g = lc if lu is None else lu + guidance * (lc - lu)
+    z = g if temperature == 1.0 else g / temperature
+    V = z.shape[-1]
+    K = int(top_k) if 0 < int(top_k) < V else V
+    if K == V and top_p >= 1.0:
+        return z
+    zs, order = torch.sort(z, dim=-1, descending=True, stable=True)          # (stable: equal values keep their index order)
+    r = torch.arange(V, device=z.device)
+    e = torch.exp(zs - zs[..., :1]) * (r < K).to(zs.dtype)
+    before = (torch.cumsum(e, dim=-1) - e) / e.sum(dim=-1, keepdim=True)
+    keep_sorted = (r < min_keep) | ((r < K) & ((before < top_p) if top_p < 1.0 else torch.ones_like(before, dtype=torch.bool)))
+    keep = torch.zeros_like(keep_sorted).scatter(-1, order, keep_sorted)
+    return torch.where(keep, z, torch.full_like(z, -float("inf")))
 
 
 @torch.no_grad()
@@ -309,9 +369,12 @@ class CachedDecoder:
     K/V projected once per molecule and shared by its k beams (cache slots sketched at
     xbert.py:291-295,480,1344-1348)."""
 
-    def __init__(self, model, prop_embeds: torch.Tensor | None, k: int, Lmax: int, repeat: int = 1, xkv: dict | None = None, memory: dict | None = None):
+    def __init__(self, model, prop_embeds: torch.Tensor | None, k: int, Lmax: int, repeat: int = 1, xkv: dict | None = None, memory: dict | None = None,
+                 src: torch.Tensor | None = None):
         """repeat: decode `repeat` molecules per row of prop_embeds (generation of many samples from one PV: the cross-attention keys /
         values are projected once per row and copied).  xkv: the projections of an earlier decoder on the same prop_embeds (`xkv_once`).
+        src (host int64 [N], instead of repeat): molecule n decodes against row src[n] of prop_embeds -- `repeat` for any assignment
+        (GuidedDecoder: N molecules on their conditions, N more on the one all-masked row).
         memory (instead of prop_embeds): a masked, variable-length cross-attention memory, one source per molecule -- dict(N, xkv = {layer:
         bf16 [M, 2H] keys | values of token-major rows}, row0 / len = int32 [N] first row and length of every source, Lmax = the longest
         length allowed) -- read through spmm_decode_xattn; it is never moved: `compact` gathers the molecule -> source index alone."""
@@ -327,6 +390,10 @@ class CachedDecoder:
             N, Lkv, H = memory["N"], memory["Lmax"], c.hidden_size
         else:
             N, Lkv, H = prop_embeds.shape
+        self.src = None if src is None else torch.as_tensor(src).detach().cpu().to(torch.int64).reshape(-1)
+        if self.src is not None:
+            assert memory is None and repeat == 1 and int(self.src.min()) >= 0 and int(self.src.max()) < N
+            N = self.src.numel()
         N *= repeat
         assert Lmax <= 256 and H == c.hidden_size and c.hidden_size // c.num_attention_heads == 64
         self.N, self.R, self.Lmax, self.Lp, self.H = N, N * k, Lmax, Lkv, H
@@ -344,7 +411,21 @@ class CachedDecoder:
         if xkv is None:
             xkv = _cross_kv(eng, self.pfx + "bert.", c, prop_embeds.to(dev).to(BF).reshape(-1, H).contiguous())
         self.xkv_once = xkv                              # per row of prop_embeds
-        self.xkv = {l: (KV.view(-1, Lkv, 2 * H).repeat_interleave(repeat, dim=0).reshape(-1, 2 * H) if repeat > 1 else KV) for l, KV in xkv.items()}
+        self._expand_xkv(xkv)
+
+    def _expand_xkv(self, xkv: dict):
+        """self.xkv: the keys | values every molecule of the batch reads, one [Lp, 2H] block per molecule, from the per-condition `xkv`."""
+        Lkv, H = self.Lp, self.H
+        if self.src is not None:
+            pick = self.src.to(self.device)
+            self.xkv = {l: KV.view(-1, Lkv, 2 * H).index_select(0, pick).reshape(-1, 2 * H) for l, KV in xkv.items()}
+        else:
+            self.xkv = {l: (KV.view(-1, Lkv, 2 * H).repeat_interleave(self.repeat, dim=0).reshape(-1, 2 * H) if self.repeat > 1 else KV)
+                        for l, KV in xkv.items()}
+
+    def search_tables(self) -> Tuple[torch.Tensor, torch.Tensor | None]:
+        """(anc, rowmap) as the search's beam step updates / reads them: the rows of the beams it keeps books for."""
+        return self.anc, self.rowmap
 
     @torch.no_grad()
     def compact(self, keep: torch.Tensor):
@@ -359,10 +440,23 @@ class CachedDecoder:
             cur = torch.arange(self.N, dtype=torch.int32, device=self.device) if self.kv_seq is None else self.kv_seq
             self.kv_seq = cur[keep].contiguous()
         else:
-            for l, KV in self.xkv.items():
-                self.xkv[l] = KV.view(self.N, Lp, KV.shape[1])[keep].reshape(-1, KV.shape[1]).contiguous()
+            self._compact_xkv(keep)
         self.N = int(keep.numel())
         self.R = self.N * k
+
+    def _compact_xkv(self, keep: torch.Tensor):
+        """`compact` for the per-molecule cross-attention keys | values (self.N is still the batch before the compaction)."""
+        for l, KV in self.xkv.items():
+            self.xkv[l] = KV.view(self.N, self.Lp, KV.shape[1])[keep].reshape(-1, KV.shape[1]).contiguous()
+
+    def _cross_attn(self, l: int, q: torch.Tensor, ctx: torch.Tensor):
+        """Newest-position cross-attention of fusion layer l: queries q [R, H] -> ctx, every molecule's k beams on its own keys | values."""
+        H, nH, KV = self.H, self.c.num_attention_heads, self.xkv[l]
+        if self.mem is None:
+            ops.decode_attn(q, KV[:, :H], KV[:, H:], ctx, nH=nH, Lkv=self.Lp, seq_stride=self.Lp * 2 * H, tok_stride=2 * H, kv_div=self.k, group=self.k)
+        else:
+            ops.decode_xattn(q, KV[:, :H], KV[:, H:], ctx, nH=nH, kv_seq=self.kv_seq, kv_row0=self.mem["row0"], kv_len=self.mem["len"],
+                             Lkv_max=self.Lp, group=self.k)
 
     @torch.no_grad()
     def step(self, ids: torch.Tensor, t: int, t_dev: torch.Tensor | None = None) -> torch.Tensor:
@@ -392,12 +486,7 @@ class CachedDecoder:
                 pf = lp + "crossattention."
                 q = new(R, H)
                 ops.gemm_nt(a, P.wb(pf + "self.query.weight"), q, bias=P.w(pf + "self.query.bias"))
-                KV = self.xkv[l]
-                if self.mem is None:
-                    ops.decode_attn(q, KV[:, :H], KV[:, H:], ctx, nH=nH, Lkv=self.Lp, seq_stride=self.Lp * 2 * H, tok_stride=2 * H, kv_div=self.k, group=self.k)
-                else:
-                    ops.decode_xattn(q, KV[:, :H], KV[:, H:], ctx, nH=nH, kv_seq=self.kv_seq, kv_row0=self.mem["row0"], kv_len=self.mem["len"],
-                                     Lkv_max=self.Lp, group=self.k)
+                self._cross_attn(l, q, ctx)
                 a = sub(pf + "output.", ctx, a)[0]
             h = new(R, c.intermediate_size)
             ops.gemm_nt(a, P.wb(lp + "intermediate.dense.weight"), h, bias=P.w(lp + "intermediate.dense.bias"), epi=ops.EPI_GELU)
@@ -454,7 +543,8 @@ class CachedDecoder:
         proj = {f"{TP}encoder.layer.{l}.crossattention": KV for l, KV in self.xkv_once.items()}
         cond = self.cond.to(dev).to(BF).reshape(-1, H).contiguous()
         src = KVSource(cond, cond.shape[0] // Lp, Lp, proj=proj)
-        g = Batch([Group(0, n_pairs, P, None, 0).bind(src, i32((dst.long() // k) // self.repeat), 0)])
+        mol0 = dst.long() // k                                                   # first molecule of every pair: the pair's condition is its
+        g = Batch([Group(0, n_pairs, P, None, 0).bind(src, i32(mol0 // self.repeat if self.src is None else self.src[mol0]), 0)])
         y, _, _ = eng.stack_fwd(TP, c, range(f, n), True, text, g, False, kv_tap=functools.partial(fill, row0_hi))
         self.anc[:, :P] = dst_d[pom.to(dev)].repeat_interleave(k)[:, None]
         last = y.index_select(0, (torch.arange(n_pairs) * P + P - 1).to(dev))
@@ -470,8 +560,150 @@ class CachedDecoder:
         torch.where(self.cols >= t, self.rows[:, None], anc, out=self.anc)
 
 
+class GuidedDecoder(CachedDecoder):
+    """CachedDecoder whose `step` / `prefill` return WARPED logits (warp_logits' rules): temperature, top-k and nucleus truncation, and --
+    with base_embeds -- classifier-free guidance against the decoder's own all-masked prediction.
+    Guidance runs both conditions in ONE set of launches: the decoder holds 2N molecules, rows [0, R) on their conditions and rows
+    [R, 2R) on the baseline (R = N * k), the all-masked PV encoded and projected once (base_embeds [1, Lp, H]: with every property
+    masked the encoding does not depend on the PV) and its keys | values shared by all N baseline molecules: their cross-attention is a
+    second launch per fusion layer that reads the one block with sequence stride 0.
+    Both halves are fed the same tokens; ops.logit_warp combines the two halves of the logits (lu = lc + R * ld) in place, and the search
+    sees [R, V] logits, anc[:R] and rowmap[:R] (`search_tables`): BeamBook, the beam step and the noise know nothing of the second half.
+    The baseline half's ancestry is the mirror anc[R + r, j] = anc[r, j] + R0 (R0: the uncompacted R; cache rows keep their indices
+    under compaction, so the offset is constant), refreshed by one small launch at the head of every step.
+    The scores the search records are log-probabilities of the warped distribution, renormalised over the kept tokens.
+    The warp is the kernel where the one-launch beam step runs (k <= 8, V <= 512, FUSED_BEAM_STEP), else warp_logits."""
+
+    def __init__(self, model, prop_embeds: torch.Tensor, k: int, Lmax: int, repeat: int = 1, xkv: dict | None = None, memory: dict | None = None, *,
+                 base_embeds: torch.Tensor | None = None, guidance: float = 1.0, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+        if memory is not None:
+            raise ValueError("guidance contrasts a property condition with the all-masked one; a decoder with memory= (reaction prediction) "
+                             "has no such baseline")
+        self.warp = check_warp(guidance, temperature, top_k, top_p, k) or dict(NO_WARP)
+        if base_embeds is None and self.warp["guidance"] != 1.0:
+            raise ValueError(f"guidance={guidance} needs base_embeds, the encoded all-masked PV")
+        Nc = prop_embeds.shape[0]
+        self.guided = base_embeds is not None
+        if self.guided:
+            N = Nc * repeat
+            conds = torch.cat([prop_embeds, base_embeds[:1].to(prop_embeds.device).to(prop_embeds.dtype)], dim=0)
+            src = torch.cat([torch.arange(Nc).repeat_interleave(repeat), torch.full((N,), Nc, dtype=torch.int64)])
+            super().__init__(model, conds, k, Lmax, xkv=xkv, src=src)
+        else:
+            super().__init__(model, prop_embeds, k, Lmax, repeat=repeat, xkv=xkv)
+        self.R0 = self.R // 2 if self.guided else self.R                  # beam rows of the search before any compaction
+        self.fused_warp = bool(FUSED_BEAM_STEP and k <= 8 and self.c.vocab_size <= 512)
+        self.warp_info = dict(self.warp, baseline_rows=self.R0 if self.guided else 0)
+
+    def _warped(self, logits: torch.Tensor, n: int) -> torch.Tensor:
+        """logits fp32 [2n, V] (guided: conditioned rows, then their baseline twins) or [n, V] -> warped [n, V], in place where the kernel runs."""
+        w = self.warp
+        lc, lu = logits[:n], (logits[n:] if self.guided else None)
+        if self.fused_warp:
+            return ops.logit_warp(lc, lu, w=w["guidance"], temperature=w["temperature"], top_k=w["top_k"], top_p=w["top_p"], min_keep=self.k)
+        return warp_logits(lc, lu, guidance=w["guidance"], temperature=w["temperature"], top_k=w["top_k"], top_p=w["top_p"], min_keep=self.k)
+
+    def _expand_xkv(self, xkv: dict):
+        """The conditioned half as CachedDecoder expands it; the baseline half reads ONE copy, the all-masked row's projection."""
+        if not self.guided:
+            return super()._expand_xkv(xkv)
+        Lp, H, n = self.Lp, self.H, self.N // 2
+        pick = self.src[:n].to(self.device)
+        self.xkv = {l: KV.view(-1, Lp, 2 * H).index_select(0, pick).reshape(-1, 2 * H) for l, KV in xkv.items()}
+        self.xkv_base = {l: KV.view(-1, Lp, 2 * H)[-1] for l, KV in xkv.items()}        # [Lp, 2H] views of xkv_once
+
+    def _compact_xkv(self, keep: torch.Tensor):
+        if not self.guided:
+            return super()._compact_xkv(keep)
+        n = self.N // 2                                                   # (keep = the kept slots of the first half, then their twins)
+        for l, KV in self.xkv.items():
+            self.xkv[l] = KV.view(n, self.Lp, KV.shape[1])[keep[:keep.numel() // 2]].reshape(-1, KV.shape[1]).contiguous()
+
+    def _cross_attn(self, l: int, q: torch.Tensor, ctx: torch.Tensor):
+        """Two launches: the conditioned rows on their molecules' keys | values, the baseline rows all on the one all-masked block
+        (sequence stride 0: every molecule's "own" block is block 0)."""
+        if not self.guided:
+            return super()._cross_attn(l, q, ctx)
+        H, nH, R, KV, B = self.H, self.c.num_attention_heads, self.R // 2, self.xkv[l], self.xkv_base[l]
+        ops.decode_attn(q[:R], KV[:, :H], KV[:, H:], ctx[:R], nH=nH, Lkv=self.Lp, seq_stride=self.Lp * 2 * H, tok_stride=2 * H, kv_div=self.k, group=self.k)
+        ops.decode_attn(q[R:], B[:, :H], B[:, H:], ctx[R:], nH=nH, Lkv=self.Lp, seq_stride=0, tok_stride=2 * H, kv_div=self.k, group=self.k)
+
+    def search_tables(self):
+        R = self.R // 2 if self.guided else self.R
+        return self.anc[:R], (None if self.rowmap is None else self.rowmap[:R])
+
+    @torch.no_grad()
+    def step(self, ids: torch.Tensor, t: int, t_dev: torch.Tensor | None = None) -> torch.Tensor:
+        """ids [R]: the token at position t of every beam of the search -> warped fp32 logits [R, V] for position t + 1."""
+        if not self.guided:
+            return self._warped(super().step(ids, t, t_dev), self.R)
+        R = self.R // 2
+        assert ids.numel() == R, (ids.shape, R)
+        torch.add(self.anc[:R], self.R0, out=self.anc[R:])               # the mirror: what the beam step did to the first half since the last step
+        ids = ids.to(torch.int32)
+        return self._warped(super().step(torch.cat([ids, ids]), t, t_dev), R)
+
+    @torch.no_grad()
+    def compact(self, keep: torch.Tensor):
+        """`keep` (slots of the search's batch) -> the same molecules of both halves."""
+        super().compact(torch.cat([keep, keep + self.N // 2]) if self.guided else keep)
+
+    @torch.no_grad()
+    def reorder(self, parent: torch.Tensor, t):
+        super().reorder(torch.cat([parent, parent], dim=0) if self.guided else parent, t)
+
+    @torch.no_grad()
+    def prefill(self, prefix_ids: torch.Tensor, pair_of_molecule, by_steps: bool = False) -> torch.Tensor:
+        """CachedDecoder.prefill -> the WARPED logits [Npairs, V] of the pairs.  Guided: every (condition, prefix) pair gets a baseline twin
+        (pair p + Npairs, the start of the baseline molecules of p's molecules), so the unimodal layers still run once per distinct
+        prefix, and the twin's cache row is the pair's + R0 -- what the mirror expects."""
+        k, N = self.k, (self.N // 2 if self.guided else self.N)
+        pom, dst = _prefix_rows(prefix_ids, pair_of_molecule, N, k)
+        n_pairs = prefix_ids.shape[0]
+        if by_steps:                                                      # the stepping twin: this class's own (two-half, warped) step
+            rows = prefix_ids.detach().cpu().to(torch.int64)[pom].repeat_interleave(k, dim=0).to(self.device)
+            for j in range(rows.shape[1]):
+                logits = self.step(rows[:, j].contiguous(), j)
+            return logits[dst.to(self.device).long()]
+        if not self.guided:
+            return self._warped(super().prefill(prefix_ids, pom), n_pairs)
+        logits = super().prefill(torch.cat([prefix_ids, prefix_ids], dim=0), torch.cat([pom, pom + n_pairs]))
+        return self._warped(logits, n_pairs)
+
+
+class GuidedRecompute:
+    """GuidedDecoder's twin on whole-prefix forwards (RecomputeDecoder: any model with the module API, the CPU oracle included): one
+    decoder per condition and warp_logits.  The yard-stick of the cached route."""
+
+    def __init__(self, model, prop_embeds: torch.Tensor, k: int, Lmax: int, *, base_embeds: torch.Tensor | None = None, guidance: float = 1.0,
+                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+        self.warp = check_warp(guidance, temperature, top_k, top_p, k) or dict(NO_WARP)
+        if base_embeds is None and self.warp["guidance"] != 1.0:
+            raise ValueError(f"guidance={guidance} needs base_embeds, the encoded all-masked PV")
+        self.k, self.device = k, prop_embeds.device
+        self.cond = RecomputeDecoder(model, prop_embeds, k, Lmax)
+        self.base = None if base_embeds is None else RecomputeDecoder(model, base_embeds[:1].expand(prop_embeds.shape[0], -1, -1), k, Lmax)
+        self.warp_info = dict(self.warp, baseline_rows=0 if self.base is None else prop_embeds.shape[0] * k)
+
+    def _warped(self, lc, lu):
+        w = self.warp
+        return warp_logits(lc.float(), None if lu is None else lu.float(), guidance=w["guidance"], temperature=w["temperature"], top_k=w["top_k"],
+                           top_p=w["top_p"], min_keep=self.k)
+
+    def step(self, ids: torch.Tensor, t: int) -> torch.Tensor:
+        return self._warped(self.cond.step(ids, t), None if self.base is None else self.base.step(ids, t))
+
+    def prefill(self, prefix_ids: torch.Tensor, pair_of_molecule, by_steps: bool = False) -> torch.Tensor:
+        return self._warped(self.cond.prefill(prefix_ids, pair_of_molecule), None if self.base is None else self.base.prefill(prefix_ids, pair_of_molecule))
+
+    def reorder(self, parent: torch.Tensor, t: int):
+        self.cond.reorder(parent, t)
+        if self.base is not None:
+            self.base.reorder(parent, t)
+
+
 PAD_ID = 0
-DECODE_MAXL = 256               # positions the decode kernels hold (spmm_decode_attn, spmm_beam_step, spmm_gumbel_noise)
+DECODE_MAXL = 256              # positions the decode kernels hold (spmm_decode_attn, spmm_beam_step, spmm_gumbel_noise)
 
 
 def check_prefix(prefix, N: int, vocab_size: int | None, max_steps: int) -> torch.Tensor | None:
@@ -517,7 +749,8 @@ def _vocab_size(model) -> int | None:
 def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int = 100, cached: bool | None = None,
                         sync_every: int = 4, prop_mask: torch.Tensor | None = None, stochastic: bool = False,
                         generator=None, graph: bool | None = None, compact: bool = True, seed: int | None = None,
-                        mol_base: int = 0, prefix=None, prefill: bool = True) -> List[List[Tuple[float, List[int]]]]:
+                        mol_base: int = 0, prefix=None, prefill: bool = True, guidance: float = 1.0, temperature: float = 1.0, top_k: int = 0,
+                        top_p: float = 1.0) -> List[List[Tuple[float, List[int]]]]:
     """The reference's beam search for N molecules at once (props [N,53]); result[n] is what the one-molecule search
     (oracle/decode_oracle.py::beam_search) returns for props[n].
     cached=True (default on the HIP model) decodes one token per step against the K/V cache; cached=False re-runs the prefix
@@ -542,7 +775,18 @@ def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int =
     prefill=True: the prefix goes through the decoder once, in one packed pass, into one cache row per molecule that all its beams read
     (CachedDecoder.prefill); prefill=False: it is stepped through position by position on every beam row (the twin on the existing
     kernels).  cached=False seeds the whole-prefix forward with the tokens.  A search with a prefix stays eager whatever `graph` says.
-    prefix=None, or [CLS] alone, is the search without a prefix, unchanged."""
+    prefix=None, or [CLS] alone, is the search without a prefix, unchanged.
+    guidance, temperature, top_k, top_p: the distribution every position picks or draws from (warp_logits' rules, min_keep = k), the first
+    pick from [CLS] or from the prefix logits included, on the deterministic search and the sampled ones alike.  guidance w != 1 is
+    classifier-free guidance, log p~ = log p_u + w (log p_c - log p_u), between the search's condition (props, prop_mask) and the all-masked
+    PV -- pretraining masks every property with probability 0.5, so the one decoder is also the baseline; w > 1 pushes towards the
+    requested properties, w = 0 is the all-masked model.  Both conditions run as two halves of one set of launches (GuidedDecoder;
+    cached=False: two whole-prefix decoders and warp_logits).  The scores returned are log-probabilities of the warped distribution,
+    renormalised over the kept tokens.  The seeded draws stay keyed by (seed, global molecule, absolute position, beam, token).
+    ValueError before anything runs for temperature <= 0, top_p outside (0, 1], top_k < 0 or in [1, k), a non-finite guidance.  With any
+    of the four set the search stays eager whatever `graph` says; with all four at their defaults (guidance = 1 never builds the
+    baseline) it is the search without them, launch for launch.  last_run records the four and baseline_rows (0 or N*k)."""
+    warp = check_warp(guidance, temperature, top_k, top_p, k)
     if cached is None:
         cached = hasattr(model, "engine")
     prefix = check_prefix(prefix, props.shape[0], _vocab_size(model), max_steps)
@@ -551,11 +795,22 @@ def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int =
         model.engine.train_mode = False
     N = prop_embeds.shape[0]
     P = 1 if prefix is None else prefix.shape[1]
-    dec = (CachedDecoder if cached else RecomputeDecoder)(model, prop_embeds, k, P + max_steps + 2)
+    if warp is None:
+        dec = (CachedDecoder if cached else RecomputeDecoder)(model, prop_embeds, k, P + max_steps + 2)
+    else:
+        base = _baseline_embeds(model, props[:1]) if warp["guidance"] != 1.0 else None
+        dec = (GuidedDecoder if cached else GuidedRecompute)(model, prop_embeds, k, P + max_steps + 2, base_embeds=base, **warp)
+        graph = False
     if prefix is not None:
         prefix = prefix.expand(N, P)                     # one (PV, prefix) pair per molecule; equal prefixes share the unimodal layers
     return _search(model, dec, N, k=k, max_steps=max_steps, sync_every=sync_every, stochastic=stochastic, generator=generator,
                    graph=bool(graph), compact=compact, seed=seed, mol_base=mol_base, prefix=prefix, pair_of_molecule=range(N), prefill=prefill)
+
+
+def _baseline_embeds(model, pv: torch.Tensor) -> torch.Tensor:
+    """The baseline of guidance: a PV with every property masked, encoded -> [1, Lp, H] (the values of pv do not enter it)."""
+    pv = pv.reshape(1, -1)
+    return encode_properties(model, pv, torch.ones(1, pv.shape[1], device=pv.device))
 
 
 def _advance(dec, book: BeamBook, ids: torch.Tensor, t: int, *, t_dev: torch.Tensor | None = None, noise=None, pick=None,
@@ -568,7 +823,8 @@ def _advance(dec, book: BeamBook, ids: torch.Tensor, t: int, *, t_dev: torch.Ten
     logits = dec.step(ids, t) if t_dev is None else dec.step(ids, t, t_dev=t_dev)
     noise = None if noise is None else noise(t, book.mol)
     if book.fused:
-        return book.step_fused(logits, dec.anc, t_ptr=t_dev, t_off=0 if t_dev is None else 1, ids_out=ids_out, rowmap=dec.rowmap, noise=noise)
+        anc, rowmap = dec.search_tables()
+        return book.step_fused(logits, anc, t_ptr=t_dev, t_off=0 if t_dev is None else 1, ids_out=ids_out, rowmap=rowmap, noise=noise)
     logits = logits.view(book.N, book.k, -1).float()
     values, indices = _pick(torch.softmax(logits, dim=-1), book.k, False) if pick is None else pick(logits, noise)
     held = None if t_dev is None else t_dev.to(torch.int64) + 1          # tokens held by every live beam (host: book.t = t + 1)
@@ -611,10 +867,11 @@ def _search(model, dec, N: int, *, k: int, max_steps: int, sync_every: int = 4, 
     values, indices = pick(logits, noise_at(P - 1).view(N, k, -1)[:, 0] if seeded else None)      # (noise keyed by the absolute position)
     book.first(values, indices)
     ids = indices.reshape(N * k)
-    if graph and cached and not stochastic and prefix is None:
+    if graph and cached and not stochastic and prefix is None and not hasattr(dec, "warp_info"):
         return _decode_graphed(dec, book, ids, max_steps, sync_every)
     n_cur = N
-    last_run.update(molecules=N, compactions=0, final_batch=N, positions=0, prefix_tokens=P, prefill=bool(prefix is not None and prefill))
+    last_run.update(molecules=N, compactions=0, final_batch=N, positions=0, prefix_tokens=P, prefill=bool(prefix is not None and prefill),
+                    **getattr(dec, "warp_info", dict(NO_WARP, baseline_rows=0)))
     for s in range(max_steps):
         ids = _advance(dec, book, ids, P + s, noise=noise_at, pick=pick)
         last_run["positions"] = s + 1
@@ -642,7 +899,8 @@ def _search(model, dec, N: int, *, k: int, max_steps: int, sync_every: int = 4, 
 
 @torch.no_grad()
 def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: torch.Tensor | None = None, k: int = 2, stochastic: bool = True,
-                           seed: int = 0, max_steps: int = 100, chunk: int | None = None, prefix=None, prefill: bool = True) -> List[List[int]]:
+                           seed: int = 0, max_steps: int = 100, chunk: int | None = None, prefix=None, prefill: bool = True, guidance: float = 1.0,
+                           temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> List[List[int]]:
     """`generate_with_property` of d_pv2smiles_single.py:54-111: n_sample molecules from ONE (normalised) property vector pv [53], with the
     properties of prop_mask ([53], 1 = unspecified) replaced by the mask token.  Returns one token-id list per sample ([CLS] ... [SEP]; empty
     when the search of that sample finished nothing -- counted in last_generate["no_final"]).
@@ -653,7 +911,12 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
     prefix (token ids [P], see beam_search_batched): every sample starts with it.  It is ONE (PV, prefix) pair: each chunk runs it
     through the decoder once into cache row 0, which every beam row of every sample of the chunk reads (prefill=False: stepped through on
     every row).  The samples still do not depend on the chunking: the noise is keyed by the absolute position.
-    last_generate["prefix_tokens"] = P (1 without a prefix)."""
+    last_generate["prefix_tokens"] = P (1 without a prefix).
+    guidance, temperature, top_k, top_p: beam_search_batched's, with the same checks and defaults (all at their defaults: the run without
+    them).  The guidance baseline is this PV with every property masked; it is encoded once, and its cross-attention keys | values are
+    projected once per run next to the condition's (`xkv_once`) -- a chunk of n samples is 2 conditions x n molecules in one decoder.  The
+    samples still do not depend on the chunking.  last_generate records the four and baseline_rows."""
+    warp = check_warp(guidance, temperature, top_k, top_p, k)
     cached = hasattr(model, "engine")
     prefix = check_prefix(prefix, 1, _vocab_size(model), max_steps)
     P = 1 if prefix is None else prefix.shape[1]
@@ -664,9 +927,16 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
     rng = random.Random(seed)
     out: List[List[int]] = []
     xkv, none = None, 0
+    base_embeds = _baseline_embeds(model, pv) if warp is not None and warp["guidance"] != 1.0 else None
     for base in range(0, n_sample, chunk):
         n = min(chunk, n_sample - base)
-        if cached:
+        if warp is not None:
+            if cached:
+                dec = GuidedDecoder(model, prop_embeds, k, P + max_steps + 2, repeat=n, xkv=xkv, base_embeds=base_embeds, **warp)
+                xkv = dec.xkv_once
+            else:
+                dec = GuidedRecompute(model, prop_embeds.expand(n, -1, -1), k, P + max_steps + 2, base_embeds=base_embeds, **warp)
+        elif cached:
             dec = CachedDecoder(model, prop_embeds, k, P + max_steps + 2, repeat=n, xkv=xkv)
             xkv = dec.xkv_once
         else:
@@ -680,7 +950,8 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
             else:
                 out.append(finals[rng.randrange(len(finals)) if stochastic else 0][1])
     last_generate.clear()
-    last_generate.update(samples=n_sample, no_final=none, chunks=(n_sample + chunk - 1) // chunk, prefix_tokens=P)
+    last_generate.update(samples=n_sample, no_final=none, chunks=(n_sample + chunk - 1) // chunk, prefix_tokens=P,
+                         **{f: last_run.get(f, v) for f, v in dict(NO_WARP, baseline_rows=0).items()})
     return out
 
 

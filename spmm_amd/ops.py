@@ -623,6 +623,25 @@ def gumbel_noise(seed, N, k, V, Lmax, *, salt=0, t=0, t_ptr=None, t_off=0, mol=N
     return out
 
 
+def logit_warp(lc, lu=None, *, w=1.0, temperature=1.0, top_k=0, top_p=1.0, min_keep=1, out=None):
+    """Guidance, temperature, top-k and nucleus truncation of next-token logits in one launch (csrc/warp.hip, spmm_logit_warp; the
+    tensor-op twin is decode.warp_logits): lc fp32 [R, V] conditioned logits, lu (optional, same shape and row stride) the all-masked
+    ones -> out (default: lc, in place) holds z = (lu + w (lc - lu)) / temperature where the token is kept and -inf elsewhere.  Kept: the
+    min_keep best-ranked tokens, and of the top_k best (0: all) those whose predecessors' softmax mass is below top_p.  What the beam step
+    reads next: it records the log-probabilities of this warped distribution, renormalised over the kept tokens."""
+    assert lc.dtype == torch.float32 and lc.dim() == 2 and (lc.stride(1) == 1 or lc.shape[1] == 1)
+    R, V = lc.shape
+    if lu is not None:
+        assert lu.dtype == torch.float32 and lu.shape == lc.shape and lu.device == lc.device and (R <= 1 or lu.stride(0) == lc.stride(0))
+        assert lu.stride(1) == 1 or V == 1
+    if out is None:
+        out = lc
+    assert out.dtype == torch.float32 and out.shape == lc.shape and out.device == lc.device and (out.stride(1) == 1 or V == 1)
+    _call("spmm_logit_warp", _p(lc), _p(lu), lc.stride(0), R, V, float(w), float(temperature), int(top_k), float(top_p), int(min_keep),
+          _p(out), out.stride(0), _st())
+    return out
+
+
 def kv_prefill(K, V, row0, length, dst_row, Kc, Vc):
     """Whole prefixes into the decoder's self-attention cache (csrc/prefill.hip, spmm_kv_prefill): K / V bf16 [rows, nH*64] views of
     token-major rows with one row stride (the K and V column blocks of a fused Q|K|V projection); Kc / Vc bf16 [R, nH, Lmax, 64]
