@@ -23,9 +23,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from pv2smiles import read_normalize, synthetic_vocab      # noqa: E402  (the mean / std file is read exactly as pv2smiles.py reads it)
+# the package's batching helpers, under the names the drivers import
+from spmm_amd.tokenizer import MAX_LENGTH, encode_smiles as encode, length_sorted_batches, pad_rows as pad_batch, with_cls      # noqa: E402,F401
 
 N_PROPS = 53
-MAX_LENGTH = 100                                           # d_smiles2pv.py:43 (tokenizer(..., truncation=True, max_length=100))
 
 
 # --------------------------------------------------------------------------------------------------------------------- input
@@ -33,33 +34,6 @@ def read_smiles(path: str):
     """One SMILES per line (s2p_input.txt); blank lines are skipped."""
     with open(path) as f:
         return [line.strip() for line in f if line.strip()]
-
-
-def with_cls(smiles):
-    """pv_generate's list branch (d_smiles2pv.py:40-41): every string starts with the text '[CLS]' (with basic tokenisation off the
-    whole string is one word; the vocabulary holds the SMILES fragments only as '##' continuations, so a word must start with a piece
-    that has a plain form)."""
-    return [s if s.startswith("[CLS]") else "[CLS]" + s for s in smiles]
-
-
-def encode(tokenizer, smiles, max_length: int = MAX_LENGTH):
-    """Token ids of every molecule as the encoder sees them: the tokenizer's own [CLS] dropped (input_ids[:, 1:], d_smiles2pv.py:44),
-    truncated to max_length tokens before that."""
-    return [tokenizer.encode(s, max_length)[1:] for s in with_cls(smiles)]
-
-
-def length_sorted_batches(lengths, batch_size: int):
-    """Index arrays of the batches: molecules in order of token length (stable), `batch_size` at a time."""
-    order = np.argsort(np.asarray(lengths), kind="stable")
-    return [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
-
-
-def pad_batch(rows, pad_id: int = 0):
-    L = max(len(r) for r in rows)
-    ids = torch.full((len(rows), L), pad_id, dtype=torch.long)
-    for i, r in enumerate(rows):
-        ids[i, :len(r)] = torch.tensor(r, dtype=torch.long)
-    return ids, (ids != pad_id).long()
 
 
 def predict_all(model, tokenizer, smiles, batch_size: int, n_props: int = N_PROPS, predict=None) -> torch.Tensor:

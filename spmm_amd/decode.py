@@ -996,30 +996,24 @@ class S2PDecoder:
 
     @torch.no_grad()
     def __init__(self, model, text_ids: torch.Tensor, text_mask: torch.Tensor, n_props: int = 53):
-        from .engine import BF, KVSource, host_token_count
+        from .engine import BF, host_token_count
         eng = model.engine
         eng.train_mode = False
         self.eng, self.P, self.ct, self.cp = eng, eng.P, model.cfg.text, model.cfg.prop
         ct, cp, P, dev = self.ct, self.cp, eng.P, model.device_
-        H, f = ct.hidden_size, ct.fusion_layer
-        B, Lt = text_ids.shape
+        H = ct.hidden_size
+        B = text_ids.shape[0]
         Lc = n_props + 1
         if Lc > cp.max_position_embeddings:
             raise ValueError(f"{n_props} properties need {Lc} positions; the PV encoder has {cp.max_position_embeddings}")
-        if Lt > ct.max_position_embeddings:
-            raise ValueError(f"sequence length {Lt} exceeds the {ct.max_position_embeddings} position embeddings")
         self.B, self.n_props, self.Lc, self.H = B, n_props, Lc, H
         # ---- the text, once: embeddings, packed rows, unimodal layers
-        ids32 = text_ids.to(dev).to(torch.int32).contiguous()
-        mask32 = text_mask.to(dev).to(torch.int32).contiguous()
-        x, _ = eng.embed_text(self.TP, ct, ids32, B, Lt, False)
-        pk = eng._pack_plan(mask32, B, Lt, host_token_count(text_mask)) if (eng.pack_text and Lt <= ops.ATTN_MAXL) else None
-        x, g, _ = eng.text_rows(x, mask32, pk)
-        text, _, _ = eng.stack_fwd(self.TP, ct, range(0, f), False, x, g, False)
+        text = eng.encode_text(self.TP, ct, text_ids.to(dev).to(torch.int32).contiguous(), text_mask.to(dev).to(torch.int32).contiguous(),
+                               n_tokens=host_token_count(text_mask))
         # ---- cross-attention keys | values of every fusion layer, once
-        proj = {f"{self.TP}encoder.layer.{l}.crossattention": KV for l, KV in _cross_kv(eng, self.TP, ct, text).items()}
-        self.src = KVSource(text, B, Lt, row0=pk["row0"], length=pk["len"], proj=proj) if pk else KVSource(text, B, Lt, proj=proj)
-        self.kv_mask = None if pk else mask32            # (packed: the source's lengths are the key mask)
+        proj = {f"{self.TP}encoder.layer.{l}.crossattention": KV for l, KV in _cross_kv(eng, self.TP, ct, text.y).items()}
+        self.src = text.source(proj=proj)
+        self.kv_mask = text.kv_mask                      # (packed: the source's lengths are the key mask)
         self.ar = torch.arange(B, dtype=torch.int32, device=dev)
         # ---- index arrays of all steps, once: step i gathers rows (b, 0..i) of the cache and keeps row (b, i) for the last layer
         b_ = np.arange(B, dtype=np.int64)[:, None]
@@ -1095,26 +1089,16 @@ class RxnDecoder(CachedDecoder):
             raise ValueError(f"{k} beams: spmm_decode_xattn serves 1..8 beams per reaction")
         if Lt > ops.ATTN_MAXL:
             raise ValueError(f"reactant sequences are limited to {ops.ATTN_MAXL} tokens (got {Lt}); the reference truncates at 150")
-        if Lt > ce.max_position_embeddings:
-            raise ValueError(f"sequence length {Lt} exceeds the {ce.max_position_embeddings} position embeddings")
         host_mask = text_mask.detach().to("cpu")
         n_tokens = host_token_count(host_mask)
         if tuple(host_mask.shape) != (B, Lt) or n_tokens is None:
             raise ValueError("text_mask must be [B, Lt] right-padded prefixes with at least one token per reaction")
-        ids32 = text_ids.to(dev).to(torch.int32).contiguous()
-        mask32 = host_mask.to(dev).to(torch.int32).contiguous()
-        x, _ = eng.embed_text(self.EP, ce, ids32, B, Lt, False)
-        pk = eng._pack_plan(mask32, B, Lt, n_tokens) if eng.pack_text else None
-        x, g, _ = eng.text_rows(x, mask32, pk)
-        text, _, _ = eng.stack_fwd(self.EP, ce, range(0, ce.fusion_layer), False, x, g, False)          # mode='text'
-        lens = host_mask.sum(1).to(torch.int32)
-        if pk:
-            row0, length = pk["row0"], pk["len"]
-        else:                                            # nothing to drop (or packing switched off): the dense [B, Lt] rows
-            row0, length = (torch.arange(B, dtype=torch.int32) * Lt).to(dev), lens.to(dev)
-        memory = dict(N=B, Lmax=Lt, xkv=_cross_kv(eng, "text_encoder.bert.", model.cfg.text, text), row0=row0.contiguous(), len=length.contiguous())
+        text = eng.encode_text(self.EP, ce, text_ids.to(dev).to(torch.int32).contiguous(), host_mask.to(dev).to(torch.int32).contiguous(),
+                               n_tokens=n_tokens)                                                        # mode='text'
+        row0, length = text.tables()                     # (nothing to drop, or packing switched off: those of the dense [B, Lt] rows)
+        memory = dict(N=B, Lmax=Lt, xkv=_cross_kv(eng, "text_encoder.bert.", model.cfg.text, text.y), row0=row0.contiguous(), len=length.contiguous())
         super().__init__(model, None, k, Lmax, memory=memory)
-        self.src_len = lens                              # host: tokens per reaction
+        self.src_len = host_mask.sum(1).to(torch.int32)  # host: tokens per reaction
 
 
 class _HostBeams:

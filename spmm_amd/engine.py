@@ -23,8 +23,9 @@ from __future__ import annotations
 import contextlib
 import functools
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import ops, streams
@@ -170,15 +171,85 @@ class HeadTape:
     ln: LnTape
 
 
+def _prefix_lens(mask_h: torch.Tensor) -> Optional[torch.Tensor]:
+    """Row sums of a host mask [n, L]; None unless every row is a non-empty prefix."""
+    lens = mask_h.sum(1)
+    prefix = bool((lens > 0).all()) and bool(((torch.arange(mask_h.shape[1])[None, :] < lens[:, None]) == (mask_h != 0)).all())
+    return lens if prefix else None
+
+
+def host_lens(mask_h: torch.Tensor, what: str) -> np.ndarray:
+    """Token counts of a host mask [n, L] whose rows are non-empty prefixes (what padding a batch to its longest gives)."""
+    if mask_h.dim() != 2 or mask_h.shape[0] == 0:
+        raise ValueError(f"{what}: the attention mask must be [n, L] with n >= 1")
+    lens = _prefix_lens(mask_h)
+    if lens is None:
+        raise ValueError(f"{what}: every attention mask must be a non-empty prefix (what padding a batch to its longest gives)")
+    return lens.numpy().astype(np.int64)
+
+
 def host_token_count(mask) -> Optional[int]:
     """Valid-token count of a host mask whose rows are non-empty prefixes (what padding='longest' gives): sizes the packed layers
     (Engine._pack_plan's `n_tokens`) without a device read.  None for a device mask or another shape of mask (the pack plan then reads
     the count back itself)."""
     if not (torch.is_tensor(mask) and mask.device.type == "cpu" and mask.dim() == 2):
         return None
-    lens = mask.sum(1)
-    prefix = bool((lens > 0).all()) and bool(((torch.arange(mask.shape[1])[None, :] < lens[:, None]) == (mask != 0)).all())
-    return int(lens.sum()) if prefix else None
+    lens = _prefix_lens(mask)
+    return None if lens is None else int(lens.sum())
+
+
+class PairLayout(NamedTuple):
+    """P query sequences gathered from U distinct sequences of a text pass (TextRows.pair_layout), host arrays: pair p is `len_p[p]` rows
+    from row `qrow0[p]` of the Mt gathered rows; gathered row r is position `pos[r]` of pair `seq[r]` = row `gather[r]` of the pass."""
+    len_p: np.ndarray
+    qrow0: np.ndarray
+    Mt: int
+    pos: np.ndarray
+    seq: np.ndarray
+    gather: np.ndarray
+
+
+@dataclass
+class TextRows:
+    """One batch of token ids as the text layers take it (Engine.text_rows_of) and, after Engine.encode_text, what they made of it:
+    the valid rows of the pack plan `pk`, or -- pk None -- the dense [B * L] rows under their key mask."""
+    x: torch.Tensor                        # embedded rows, bf16 [M, H]
+    groups: Batch                          # one Group of B sequences
+    pk: Optional[dict]                     # the pack plan (ops.pack_plan), None: dense rows
+    cls_rows: torch.Tensor                 # int64 [B]: the row of position 0 of every sequence
+    ids32: torch.Tensor
+    mask32: torch.Tensor
+    B: int
+    L: int
+    esv: LnTape                            # the embedding's tape
+    y: Optional[torch.Tensor] = None       # encode_text: the output of layers 0 .. fusion_layer - 1 ...
+    tape: Optional[list] = None            # ... and their tape
+
+    @property
+    def kv_mask(self):
+        """Key padding mask of a cross-attention over these rows: a packed source implies its key padding by its lengths."""
+        return None if self.pk else self.mask32
+
+    def tables(self):
+        """-> (row0, len) int32 [B] on the device: first row and row count of every sequence, whichever layout the rows have."""
+        if self.pk:
+            return self.pk["row0"], self.pk["len"]
+        return torch.arange(self.B, dtype=torch.int32, device=self.mask32.device) * self.L, self.mask32.sum(1).to(torch.int32)
+
+    def source(self, proj=None, tables: bool = False) -> KVSource:
+        """The encoded rows as a shared cross-attention source.  Dense rows carry no tables (their consumers pass `kv_mask`) unless
+        `tables` asks for the dense ones: the attention kernels specialise on which of the two they are given."""
+        row0, length = self.tables() if (self.pk or tables) else (None, None)
+        return KVSource(self.y, self.B, self.L, row0=row0, length=length, pack_idx=self.pk["rows"] if self.pk else None, proj=proj)
+
+    def pair_layout(self, lens_u: np.ndarray, inv: np.ndarray) -> PairLayout:
+        """lens_u: the host's token counts of the B sequences; inv [P]: the sequence of every pair."""
+        row0_u = np.concatenate([[0], np.cumsum(lens_u)[:-1]]) if self.pk else np.arange(self.B, dtype=np.int64) * self.L
+        len_p = lens_u[inv]
+        qrow0 = np.concatenate([[0], np.cumsum(len_p)[:-1]])
+        pos = np.concatenate([np.arange(l) for l in len_p])
+        seq = np.repeat(np.arange(len(inv)), len_p)
+        return PairLayout(len_p, qrow0, int(len_p.sum()), pos, seq, row0_u[inv][seq] + pos)
 
 
 STREAM_TOKENS_MAX = 49152         # B x Lt above which the step runs on one stream (Engine._one_stream)
@@ -377,6 +448,26 @@ class Engine:
             return x, Batch([Group(0, B, L, mask32, B)]), torch.arange(B, dtype=torch.int64, device=self.dev) * L
         x = ops.gather_rows2(self._new(pk["M"], x.shape[1]), x, pk["rows"])
         return x, Batch([Group(0, B, L, None, B, q_row0=pk["row0"], q_len=pk["len"], nrows=pk["M"])]), pk["row0_64"]
+
+    def text_rows_of(self, pfx, c, ids32, mask32, *, n_tokens: Optional[int] = None, save=False, causal=False, what: str = "") -> TextRows:
+        """The text pass of every path that encodes SMILES rows, up to the layers: embeddings of the token ids (int32 [B, L] on the
+        device), the pack plan wherever the packed attention layouts hold the length (`n_tokens`: the host's count of valid tokens, which
+        spares the plan its device read), the rows as ONE group -- causal from sequence 0 with `causal`.  `what` prefixes the error."""
+        B, L = ids32.shape
+        if L > c.max_position_embeddings:
+            raise ValueError(f"{what}sequence length {L} exceeds the {c.max_position_embeddings} position embeddings")
+        x, esv = self.embed_text(pfx, c, ids32, B, L, save)
+        pk = self._pack_plan(mask32, B, L, n_tokens) if (self.pack_text and L <= ops.ATTN_MAXL) else None
+        x, groups, cls_rows = self.text_rows(x, mask32, pk)
+        if causal:
+            groups.groups[0].causal_from = 0
+        return TextRows(x, groups, pk, cls_rows, ids32, mask32, B, L, esv)
+
+    def encode_text(self, pfx, c, ids32, mask32, *, n_tokens: Optional[int] = None, save=False, causal=False, what: str = "") -> TextRows:
+        """`text_rows_of`, then the unimodal layers 0 .. fusion_layer - 1 over the rows: fills `y` and `tape`."""
+        t = self.text_rows_of(pfx, c, ids32, mask32, n_tokens=n_tokens, save=save, causal=causal, what=what)
+        t.y, t.tape, _ = self.stack_fwd(pfx, c, range(0, c.fusion_layer), False, t.x, t.groups, save)
+        return t
 
     # ---------------------------------------------------------------------------------------- attention block
     def _ln_res(self, x, X, X32, gamma, beta, y, md, **kw):

@@ -31,7 +31,7 @@ class FinetuneStep(Engine):
         """-> (device loss [1] or None without targets, fp32 logits [B, C]).  `n_tokens`: the host's count of valid tokens (every mask
         row a non-empty prefix), which spares the pack plan its one device read."""
         c, P = self.cfg.text, self.P
-        H, f = c.hidden_size, c.fusion_layer
+        H = c.hidden_size
         B, L = ids.shape
         if save and L > ops.ATTN_MAXL:
             raise ValueError(f"fine-tuning sequences are limited to {ops.ATTN_MAXL} tokens (got {L}); the reference truncates at 100")
@@ -41,13 +41,11 @@ class FinetuneStep(Engine):
         ops.zero_(self.step_zero)
         ids32 = ids.to(torch.int32).contiguous()
         mask32 = mask.to(torch.int32).contiguous()
-        x, esv = self.embed_text(PFX, c, ids32, B, L, save)
-        pk = self._pack_plan(mask32, B, L, n_tokens) if (self.pack_text and L <= ops.ATTN_MAXL) else None
+        t = self.text_rows_of(PFX, c, ids32, mask32, n_tokens=n_tokens, save=save)
         if n_tokens is not None:
             self.nan_flag.bitwise_or_(self.hint_bad)       # a wrong hint: the optimiser step becomes a no-op (step.py)
-        x, groups, cls_idx = self.text_rows(x, mask32, pk)
-        y, tape, _ = self.stack_fwd(PFX, c, range(0, f), False, x, groups, save)
-        cls = ops.gather_rows2(self._new(B, H), y, cls_idx)
+        t.y, t.tape, _ = self.stack_fwd(PFX, c, range(0, c.fusion_layer), False, t.x, t.groups, save)
+        cls = ops.gather_rows2(self._new(B, H), t.y, t.cls_rows)
         W2 = P.w("reg_head.2.weight")
         Wd, C = W2.shape[1], W2.shape[0]
         act, pre = self._new(B, Wd), self._new(B, Wd)
@@ -55,7 +53,7 @@ class FinetuneStep(Engine):
         logits = self._new(B, C, dtype=torch.float32)
         tgt = None if target is None else self._target(target, B, C)
         ops.task_head(act, W2, P.w("reg_head.2.bias"), logits, kind=self.kind, target=tgt, loss=None if tgt is None else self.loss)
-        self.tape = dict(B=B, L=L, pk=pk, M=y.shape[0], ids32=ids32, esv=esv, groups=groups, tape=tape, cls=cls, cls_idx=cls_idx, act=act,
+        self.tape = dict(B=B, L=L, pk=t.pk, M=t.y.shape[0], ids32=ids32, esv=t.esv, groups=t.groups, tape=t.tape, cls=cls, cls_idx=t.cls_rows, act=act,
                          pre=pre, logits=logits, target=tgt) if save else None
         return (None if tgt is None else self.loss), logits
 

@@ -20,10 +20,10 @@ import numpy as np
 import torch
 
 from . import ops
-from .engine import BF, Batch, Group, KVSource, SelfKV, host_token_count
+from .engine import BF, Batch, Group, KVSource, SelfKV, host_lens, host_token_count
+from .tokenizer import MAX_LENGTH, encode_smiles, length_sorted_batches, pad_rows      # noqa: F401  (the library's batching helpers)
 
 TP = "text_encoder.bert."
-MAX_LENGTH = 100                  # tokens per molecule, as the reference's inference scripts truncate (d_smiles2pv.py:43)
 
 
 def _engine(model):
@@ -47,27 +47,13 @@ def _normalized(eng, proj: str, X: torch.Tensor, L: int, B: int, cls_rows=None) 
     return feat
 
 
-def _encode_text(eng, cfg, ids: torch.Tensor, mask: torch.Tensor):
-    """The unimodal text layers on the valid rows of a batch -> (rows [M, H] bf16, pack plan or None, Batch, row of position 0 [B])."""
-    ct, dev = cfg.text, eng.dev
-    B, Lt = ids.shape
-    if Lt > ct.max_position_embeddings:
-        raise ValueError(f"sequence length {Lt} exceeds the {ct.max_position_embeddings} position embeddings")
-    ids32 = ids.to(dev).to(torch.int32).contiguous()
-    mask32 = mask.to(dev).to(torch.int32).contiguous()
-    x, _ = eng.embed_text(TP, ct, ids32, B, Lt, False)
-    pk = eng._pack_plan(mask32, B, Lt, host_token_count(mask)) if (eng.pack_text and Lt <= ops.ATTN_MAXL) else None
-    x, g, cls_rows = eng.text_rows(x, mask32, pk)
-    text, _, _ = eng.stack_fwd(TP, ct, range(0, ct.fusion_layer), False, x, g, False)
-    return text, pk, g, cls_rows
-
-
 @torch.no_grad()
 def smiles_features(model, ids: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """text_feat of SPMM_models.py:93-95 for a batch of token ids [B, Lt] (position 0 = the '[CLS]' token) -> fp32 [B, E], unit rows."""
     eng = _engine(model)
-    text, _, _, cls_rows = _encode_text(eng, model.cfg, ids, mask)
-    return _normalized(eng, "text_proj", text, ids.shape[1], ids.shape[0], cls_rows=cls_rows)
+    t = eng.encode_text(TP, model.cfg.text, ids.to(eng.dev).to(torch.int32).contiguous(), mask.to(eng.dev).to(torch.int32).contiguous(),
+                        n_tokens=host_token_count(mask))
+    return _normalized(eng, "text_proj", t.y, t.L, t.B, cls_rows=t.cls_rows)
 
 
 @torch.no_grad()
@@ -90,25 +76,6 @@ def pv_features(model, pv: torch.Tensor, prop_mask: Optional[torch.Tensor] = Non
 
 
 # ------------------------------------------------------------------------------------------------------------------ stage one
-def encode_smiles(tokenizer, smiles: Sequence[str], max_length: int = MAX_LENGTH) -> List[List[int]]:
-    """Token ids as the text encoder sees them at inference (d_smiles2pv.py:40-44): the string starts with the text '[CLS]', the
-    tokenizer's own [CLS] is dropped."""
-    return [tokenizer.encode(s if s.startswith("[CLS]") else "[CLS]" + s, max_length)[1:] for s in smiles]
-
-
-def pad_rows(rows: Sequence[Sequence[int]], pad_id: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
-    L = max(len(r) for r in rows)
-    ids = torch.full((len(rows), L), pad_id, dtype=torch.long)
-    for i, r in enumerate(rows):
-        ids[i, :len(r)] = torch.as_tensor(r, dtype=torch.long)
-    return ids, (ids != pad_id).long()
-
-
-def length_sorted_batches(lengths, batch_size: int):
-    order = np.argsort(np.asarray(lengths), kind="stable")
-    return [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
-
-
 def topk_reference(q: torch.Tensor, feats: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """The tensor-library pair the kernel replaces: torch.topk(q @ feats.T, k) -- forms the [Q, N] matrix.  Yard-stick of the bench."""
     v, i = torch.topk(q @ feats.T, min(k, feats.shape[0]), dim=1)
@@ -192,15 +159,6 @@ class MoleculeIndex:
 
 
 # ------------------------------------------------------------------------------------------------------------------ stage two
-def _host_lens(mask_h: torch.Tensor) -> np.ndarray:
-    lens = mask_h.sum(1)
-    L = mask_h.shape[1]
-    prefix = bool((lens > 0).all()) and bool(((torch.arange(L)[None, :] < lens[:, None]) == (mask_h != 0)).all())
-    if not prefix:
-        raise ValueError("match_scores: every attention mask must be a non-empty prefix (what padding a batch to its longest gives)")
-    return lens.numpy().astype(np.int64)
-
-
 @torch.no_grad()
 def match_scores(model, pv_hidden: torch.Tensor, ids: torch.Tensor, mask: torch.Tensor, pairs: torch.Tensor, engine: bool = True) -> torch.Tensor:
     """Matching probability of P (query, molecule) pairs: pairs int64 [P, 2] = (row of pv_hidden, row of ids / mask) -> fp32 [P] =
@@ -228,27 +186,26 @@ def match_scores(model, pv_hidden: torch.Tensor, ids: torch.Tensor, mask: torch.
     H, Lp, f, n = ct.hidden_size, cfg.n_props + 1, ct.fusion_layer, ct.num_hidden_layers
     qs, inv_q = torch.unique(pairs_h[:, 0], return_inverse=True)
     ms, inv_m = torch.unique(pairs_h[:, 1], return_inverse=True)
-    Up, Ut = qs.numel(), ms.numel()
+    Up = qs.numel()
     # ---- every distinct molecule's text, once, on packed rows (cut to the longest of them)
-    lens_u = _host_lens(mask_h[ms])
+    lens_u = host_lens(mask_h[ms], "match_scores")
     Lt = int(lens_u.max())
     if Lt > ops.ATTN_MAXL:
         raise ValueError(f"match_scores: a molecule of {Lt} tokens exceeds the {ops.ATTN_MAXL} the packed attention layouts hold")
-    text, pk, _, _ = _encode_text(eng, cfg, ids_h[ms, :Lt], mask_h[ms, :Lt])
-    row0_u = np.concatenate([[0], np.cumsum(lens_u)[:-1]]) if pk else np.arange(Ut, dtype=np.int64) * Lt      # (dense: every molecule is Lt long)
+    mask_u = mask_h[ms, :Lt]
+    t = eng.encode_text(TP, ct, ids_h[ms, :Lt].to(dev).to(torch.int32).contiguous(), mask_u.to(dev).to(torch.int32).contiguous(),
+                        n_tokens=host_token_count(mask_u))
+    text = t.y
     i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)                        # noqa: E731
     i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)                        # noqa: E731
-    src_text = KVSource(text, Ut, Lt, row0=i32(row0_u), length=i32(lens_u))
+    src_text = t.source(tables=True)                                              # (dense: every molecule is Lt long)
     pvh = pv_hidden.to(dev).to(BF)[qs.to(dev)].reshape(Up * Lp, H).contiguous()
     src_pv = KVSource(pvh, Up, Lp)
     # ---- the fusion batch: [P PV-query sequences, dense | P text-query sequences, packed]
     iq, im = inv_q.numpy(), inv_m.numpy()
-    len_p = lens_u[im]
-    qrow0 = np.concatenate([[0], np.cumsum(len_p)[:-1]])
-    Mt = int(len_p.sum())
+    len_p, qrow0, Mt, _, _, gat_tx = t.pair_layout(lens_u, im)
     o_t = P * Lp
     gat_pv = (iq[:, None] * Lp + np.arange(Lp)[None, :]).reshape(-1)
-    gat_tx = np.concatenate([row0_u[u] + np.arange(l) for u, l in zip(im, len_p)])
     X = torch.cat([pvh.index_select(0, i64(gat_pv)), text.index_select(0, i64(gat_tx))])
     kv_m, kv_q = i32(im), i32(iq)
     qrow0_d, qlen_d = i32(qrow0), i32(len_p)

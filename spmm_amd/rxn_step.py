@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .engine import Engine, KVSource, _ceil
+from .engine import Engine, _ceil
 from .finetune_step import FinetuneStep
 
 DEC, ENC = "text_encoder.", "text_encoder2."
@@ -28,14 +28,6 @@ class RxnStep(Engine):
         self.loss = self.losses[0:1]                       # (zeroed with the rest of step_zero at the head of every forward)
 
     to_device = FinetuneStep.to_device
-
-    def _rows(self, pfx, c, ids32, mask32, n_tokens, save):
-        """Embedded text as the layers take it -> (rows, Batch, embedding tape, pack plan or None)."""
-        B, L = ids32.shape
-        x, esv = self.embed_text(pfx, c, ids32, B, L, save)
-        pk = self._pack_plan(mask32, B, L, n_tokens) if (self.pack_text and L <= ops.ATTN_MAXL) else None
-        x, groups, _ = self.text_rows(x, mask32, pk)
-        return x, groups, esv, pk
 
     def forward(self, src_ids: torch.Tensor, src_mask: torch.Tensor, prod_ids: torch.Tensor, prod_mask: torch.Tensor, *, save: bool = True,
                 n_src_tokens: Optional[int] = None, n_prod_tokens: Optional[int] = None, grad_in_forward: bool = False):
@@ -57,28 +49,26 @@ class RxnStep(Engine):
         sids32, smask32 = src_ids.to(torch.int32).contiguous(), src_mask.to(torch.int32).contiguous()
         pids32, pmask32 = prod_ids.to(torch.int32).contiguous(), prod_mask.to(torch.int32).contiguous()
         # ---- reactants (SPMM_models_rxn.py:34)
-        xs, gs, esv_s, pks = self._rows(ENC + "bert.", ce, sids32, smask32, n_src_tokens, save)
-        ys, tape_s, _ = self.stack_fwd(ENC + "bert.", ce, range(0, ce.fusion_layer), False, xs, gs, save)
-        src = KVSource(ys, B, Ls, row0=pks["row0"], length=pks["len"], pack_idx=pks["rows"]) if pks else KVSource(ys, B, Ls)
+        ts = self.encode_text(ENC + "bert.", ce, sids32, smask32, n_tokens=n_src_tokens, save=save)
+        src = ts.source()
         # ---- product (:35-42): one group of B sequences, causal from sequence 0, sequence s attending source s
-        xp, gp, esv_p, pkp = self._rows(DEC + "bert.", cd, pids32, pmask32, n_prod_tokens, save)
+        tp = self.text_rows_of(DEC + "bert.", cd, pids32, pmask32, n_tokens=n_prod_tokens, save=save, causal=True)
         if n_src_tokens is not None or n_prod_tokens is not None:
             self.nan_flag.bitwise_or_(self.hint_bad)       # a wrong hint: the optimiser step becomes a no-op (step.py)
+        gp, pkp = tp.groups, tp.pk
         g = gp.groups[0]
-        g.causal_from = 0
-        if not pks:
-            g.kv_mask = smask32                            # (a packed source implies its key padding by its lengths)
+        g.kv_mask = ts.kv_mask
         g.attend(src, torch.arange(B, dtype=torch.int64, device=self.dev))
         src.finalize()
-        yp, tape_p, _ = self.stack_fwd(DEC + "bert.", cd, range(0, cd.num_hidden_layers), True, xp, gp, save)
+        yp, tape_p, _ = self.stack_fwd(DEC + "bert.", cd, range(0, cd.num_hidden_layers), True, tp.x, gp, save)
         logits, lmsv = self.lm_head_fwd(DEC, cd, yp, save)
         # ---- CrossEntropyLoss(ignore_index=0) on the shifted product (:44-45)
         row_of = pkp["rows"] if pkp else None
         dlogits = self._new(yp.shape[0], _ceil(cd.vocab_size, 64)) if (save and grad_in_forward) else None
         ops.s2s_loss(logits, pids32.view(-1), nseq=B, L=Lp, V=cd.vocab_size, ws=self.icount[0:4], losses=self.losses, slot=0, row_of=row_of,
                      dlogits=dlogits, gscale=self.gscale[0:1] if dlogits is not None else None)
-        self.tape = dict(B=B, Ls=Ls, Lp=Lp, pks=pks, pkp=pkp, sids32=sids32, pids32=pids32, esv_s=esv_s, esv_p=esv_p, gs=gs, gp=gp, src=src,
-                         tape_s=tape_s, tape_p=tape_p, logits=logits, lmsv=lmsv, row_of=row_of, dlogits=dlogits) if save else None
+        self.tape = dict(B=B, Ls=Ls, Lp=Lp, pks=ts.pk, pkp=pkp, sids32=sids32, pids32=pids32, esv_s=ts.esv, esv_p=tp.esv, gs=ts.groups, gp=gp, src=src,
+                         tape_s=ts.tape, tape_p=tape_p, logits=logits, lmsv=lmsv, row_of=row_of, dlogits=dlogits) if save else None
         return self.loss
 
     def backward(self):

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .engine import BF, KVSource, Group, Batch, host_token_count
+from .engine import BF, KVSource, Group, Batch, host_lens, host_token_count      # noqa: F401  (host_lens: importable from here too)
 
 TP, EP = "text_encoder.bert.", "text_encoder2.bert."
 
@@ -49,18 +49,6 @@ def _engine(model):
                         "none -- the engine path is HIP kernels and has no CPU / eager fallback (engine=False runs on the module API)")
     eng.train_mode = False
     return eng
-
-
-def host_lens(mask_h: torch.Tensor, what: str) -> np.ndarray:
-    """Token counts of a host mask [n, L] whose rows are non-empty prefixes (what padding a batch to its longest gives)."""
-    if mask_h.dim() != 2 or mask_h.shape[0] == 0:
-        raise ValueError(f"{what}: the attention mask must be [n, L] with n >= 1")
-    lens = mask_h.sum(1)
-    L = mask_h.shape[1]
-    prefix = bool((lens > 0).all()) and bool(((torch.arange(L)[None, :] < lens[:, None]) == (mask_h != 0)).all())
-    if not prefix:
-        raise ValueError(f"{what}: every attention mask must be a non-empty prefix (what padding a batch to its longest gives)")
-    return lens.numpy().astype(np.int64)
 
 
 def check_pairs(pairs: Optional[torch.Tensor], n_cond: int, n_seq: int, what: str) -> torch.Tensor:
@@ -104,11 +92,9 @@ def _decode_scores(eng, ct, ids_h, lens_all, pairs_h, src: KVSource, fused: bool
     f, n = ct.fusion_layer, ct.num_hidden_layers
     ms, inv_m = torch.unique(pairs_h[:, 1], return_inverse=True)
     lens_u = lens_all[ms.numpy()]
-    Lt, Ut = int(lens_u.max()), ms.numel()
+    Lt = int(lens_u.max())
     if Lt > ops.ATTN_MAXL:
         raise ValueError(f"{what}: a sequence of {Lt} tokens exceeds the {ops.ATTN_MAXL} the packed attention layouts hold")
-    if Lt > ct.max_position_embeddings:
-        raise ValueError(f"{what}: sequence length {Lt} exceeds the {ct.max_position_embeddings} position embeddings")
     if Lt < 2:                                             # nothing but [CLS]: no position has a target
         return Scores(torch.zeros(P, dtype=torch.float32, device=dev), torch.zeros(P, dtype=torch.int64, device=dev),
                       torch.zeros(P, max(L_out - 1, 0), dtype=torch.float32, device=dev))
@@ -117,21 +103,12 @@ def _decode_scores(eng, ct, ids_h, lens_all, pairs_h, src: KVSource, fused: bool
     # ---- the unimodal layers, causal, once per distinct sequence, on packed rows
     ids_u = ids_h[ms, :Lt].contiguous()
     mask_u = (torch.arange(Lt)[None, :] < torch.from_numpy(lens_u)[:, None]).to(torch.int32)
-    ids32, mask32 = ids_u.to(dev).to(torch.int32).contiguous(), mask_u.to(dev).contiguous()
-    x, _ = eng.embed_text(TP, ct, ids32, Ut, Lt, False)
-    pk = eng._pack_plan(mask32, Ut, Lt, int(lens_u.sum())) if eng.pack_text else None
-    x, g, _ = eng.text_rows(x, mask32, pk)
-    g.groups[0].causal_from = 0
-    text, _, _ = eng.stack_fwd(TP, ct, range(0, f), False, x, g, False)
-    row0_u = np.concatenate([[0], np.cumsum(lens_u)[:-1]]) if pk else np.arange(Ut, dtype=np.int64) * Lt
+    ids32 = ids_u.to(dev).to(torch.int32).contiguous()
+    t = eng.encode_text(TP, ct, ids32, mask_u.to(dev).contiguous(), n_tokens=int(lens_u.sum()), causal=True, what=what + ": ")
     # ---- the fusion layers: P query sequences gathered from those rows, packed, causal, pair p bound to its condition
     im, iq = inv_m.numpy(), pairs_h[:, 0].numpy()
-    len_p = lens_u[im]
-    qrow0 = np.concatenate([[0], np.cumsum(len_p)[:-1]])
-    Mt = int(len_p.sum())
-    pos = np.concatenate([np.arange(l) for l in len_p])
-    seq = np.repeat(np.arange(P), len_p)
-    X = text.index_select(0, i64(row0_u[im][seq] + pos))
+    len_p, qrow0, Mt, pos, seq, gat = t.pair_layout(lens_u, im)
+    X = t.y.index_select(0, i64(gat))
     qrow0_d, qlen_d = i32(qrow0), i32(len_p)
     gq = Batch([Group(0, P, Lt, None, 0, q_row0=qrow0_d, q_len=qlen_d, nrows=Mt).bind(src, i32(iq), 0)])
     y, _, _ = eng.stack_fwd(TP, ct, range(f, n), True, X, gq, False)
@@ -243,19 +220,12 @@ def score_products(model, src_ids: torch.Tensor, src_mask: torch.Tensor, prod_id
     ce, dev = model.cfg_enc, eng.dev
     ss, inv_s = torch.unique(pairs_h[:, 0], return_inverse=True)
     lens_s = slens[ss.numpy()]
-    Ls, Us = int(lens_s.max()), ss.numel()
+    Ls = int(lens_s.max())
     if Ls > ops.ATTN_MAXL:
         raise ValueError(f"{what}: reactant sequences are limited to {ops.ATTN_MAXL} tokens (got {Ls}); the reference truncates at 150")
-    if Ls > ce.max_position_embeddings:
-        raise ValueError(f"{what}: sequence length {Ls} exceeds the {ce.max_position_embeddings} position embeddings")
     # ---- every distinct source, once, through text_encoder2 on packed rows (as decode.RxnDecoder encodes its memory)
     mask_s = (torch.arange(Ls)[None, :] < torch.from_numpy(lens_s)[:, None]).to(torch.int32)
-    ids32, mask32 = sids_h[ss, :Ls].to(dev).to(torch.int32).contiguous(), mask_s.to(dev).contiguous()
-    x, _ = eng.embed_text(EP, ce, ids32, Us, Ls, False)
-    pk = eng._pack_plan(mask32, Us, Ls, host_token_count(mask_s)) if eng.pack_text else None
-    x, g, _ = eng.text_rows(x, mask32, pk)
-    mem, _, _ = eng.stack_fwd(EP, ce, range(0, ce.fusion_layer), False, x, g, False)
-    row0 = np.concatenate([[0], np.cumsum(lens_s)[:-1]]) if pk else np.arange(Us, dtype=np.int64) * Ls
-    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)                        # noqa: E731
-    src = KVSource(mem, Us, Ls, row0=i32(row0), length=i32(lens_s))
+    mem = eng.encode_text(EP, ce, sids_h[ss, :Ls].to(dev).to(torch.int32).contiguous(), mask_s.to(dev).contiguous(),
+                          n_tokens=host_token_count(mask_s), what=what + ": ")
+    src = mem.source(tables=True)
     return _decode_scores(eng, model.cfg.text, pids_h, plens, torch.stack([inv_s, pairs_h[:, 1]], dim=1), src, fused, L, what)

@@ -13,11 +13,13 @@ Only what the path uses is implemented: batch call with padding='longest', trunc
 from __future__ import annotations
 
 from types import SimpleNamespace
-from typing import Dict, Iterable, List, Sequence, Union
+from typing import Dict, Iterable, List, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 
 PAD, UNK, CLS, SEP = "[PAD]", "[UNK]", "[CLS]", "[SEP]"
+MAX_LENGTH = 100                  # tokens per molecule, as the reference's inference scripts truncate (d_smiles2pv.py:43)
 
 
 class SmilesWordPiece:
@@ -91,3 +93,31 @@ class SmilesWordPiece:
                 continue
             parts.append(t[2:] if t.startswith("##") else t)
         return "".join(parts)
+
+
+# -- batching helpers of the inference paths and drivers -----------------------------------------------------------------
+def with_cls(smiles: Sequence[str]) -> List[str]:
+    """pv_generate's list branch (d_smiles2pv.py:40-41): every string starts with the text '[CLS]' (with basic tokenisation off the
+    whole string is one word; the vocabulary holds the SMILES fragments only as '##' continuations, so a word must start with a piece
+    that has a plain form)."""
+    return [s if s.startswith("[CLS]") else "[CLS]" + s for s in smiles]
+
+
+def encode_smiles(tokenizer, smiles: Sequence[str], max_length: int = MAX_LENGTH) -> List[List[int]]:
+    """Token ids of every molecule as the encoder sees them: the tokenizer's own [CLS] dropped (input_ids[:, 1:], d_smiles2pv.py:44),
+    truncated to max_length tokens before that."""
+    return [tokenizer.encode(s, max_length)[1:] for s in with_cls(smiles)]
+
+
+def pad_rows(rows: Sequence[Sequence[int]], pad_id: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    L = max(len(r) for r in rows)
+    ids = torch.full((len(rows), L), pad_id, dtype=torch.long)
+    for i, r in enumerate(rows):
+        ids[i, :len(r)] = torch.as_tensor(r, dtype=torch.long)
+    return ids, (ids != pad_id).long()
+
+
+def length_sorted_batches(lengths, batch_size: int):
+    """Index arrays of the batches: molecules in order of token length (stable), `batch_size` at a time."""
+    order = np.argsort(np.asarray(lengths), kind="stable")
+    return [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
