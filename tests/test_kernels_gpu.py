@@ -419,7 +419,9 @@ def _xattn_composite(ops, Q, K, V, Wo, bo, R, gamma, beta, *, nseq, nH, Lq, Lkv,
 def test_fused_cross_attention_block(ops, nH, nseq, U, Lq, Lkv, packed, drop):
     """spmm_xattn_fwd (ONE launch: attention core + output projection + dropout + residual + LayerNorm) against (a) the composite
     it replaces -- same kernels' dropout masks, so y / z / ctx / lse / mean / rstd must agree to bf16 rounding of the intermediate
-    x (the fused kernel keeps it in fp32) -- and (b) plain fp32 torch of xbert.py:305-354 + :369-373 (dropout off)."""
+    x (both forms round it to bf16, the fused kernel in its epilogue "exactly as the projection GEMM of the composite rounds it"; the two
+    fp32 sums run in different orders, so a rounding may fall the other way) -- and (b) plain fp32 torch of xbert.py:305-354 + :369-373
+    (dropout off).  Every instantiation, panel count and output configuration against float64: tests/test_xattn_block_gpu.py."""
     H = nH * 64
     g = torch.Generator().manual_seed(nseq * 7 + Lq)
     idx = torch.randint(0, U, (nseq,), generator=g); idx[:U] = torch.arange(U)
@@ -459,7 +461,8 @@ def test_fused_cross_attention_block(ops, nH, nseq, U, Lq, Lkv, packed, drop):
     else:
         assert torch.equal(out["lse"], ref["lse"])
     assert torch.equal(out["ctx"], ref["ctx"])                   # the same arithmetic, MFMA for MFMA
-    # x is rounded to bf16 between GEMM and LayerNorm in the composite only: |dz| <= 2^-8 |x| (x up to ~4 here), LayerNorm divides by ~1.5
+    # x is rounded to bf16 between projection and LayerNorm in both forms, from fp32 sums taken in different orders: where the rounding
+    # falls the other way |dz| <= 2^-8 |x| (x up to ~4 here), LayerNorm divides by ~1.5
     close(out["z"], ref["z"], atol=4e-2, rtol=1e-2, name="z")
     close(out["y"], ref["y"], atol=4e-2, rtol=1e-2, name="y")
     close(out["mean"], ref["mean"], atol=2e-3, rtol=1e-3, name="mean")
