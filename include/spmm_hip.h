@@ -265,6 +265,28 @@ int spmm_gumbel_noise(const uint64_t* seed_ptr, uint64_t salt, int N, int k, int
 int spmm_logit_warp(const float* lc, const float* lu, long ld, int R, int V, float w, float temperature, int top_k, float top_p,
                     int min_keep, float* out, long ldo, spmm_stream_t stream);
 
+/* Grammar mask of the syntax-constrained PV -> SMILES search (csrc/syntax.hip; grammar, cost and table layout: spmm_amd/smiles_syntax.py,
+ * which is normative): one launch that strikes, in place, every next-token logit of R beam rows that cannot follow the row's own token
+ * history in a well-formed SMILES string ending inside the position budget.  SYNTAX ONLY: parentheses, ring-bond digits, bracket atoms,
+ * bond and dot placement, a non-empty molecule; not element symbols, valence, aromaticity, `%nn` ring labels ('%' rejects) or `C11`.
+ * logits, logits2 (may be null; e.g. the guidance baseline): fp32 [R, V], row stride ld; logits2 receives the identical mask.
+ * tokens: int32 histories, row stride tok_ld ELEMENTS, hist_rows rows; beam row i reads history row (mol ? mol[i / k] : i / k) * k + i % k
+ * (spmm_beam_step's convention; a row index outside [0, hist_rows) makes the row reject and is not read).  Position 0 is [CLS] and is not
+ * looked at; positions 1 .. t-1 are folded through the table; ids outside [0, V) reject.  t = tokens held by the row = the position the
+ * next token lands at, = *t_ptr + t_off when t_ptr is given (clamped into [1, t_last]); t_last = the last position the search can write.
+ * table: int32 [V, 4], 16-byte aligned (SyntaxTable.packed).  With the row's state (q, depth, rings) a token v other than [SEP] is allowed
+ * iff it does not reject from q, depth >= need[v] and cost(state after v) <= t_last - t - 1; [SEP] iff the end rule holds; a history that
+ * rejects allows nothing.  A masked entry becomes SPMM_SYNTAX_MASKED (finite: u + w (c - u) of two masked entries is the sentinel again,
+ * not NaN); an allowed entry keeps its bits; columns [V, ld) are not touched.  state_out (optional): int32 [R, 4] = (q, depth, rings, cost)
+ * of the history, (10, 0, 0, -1) for a history that rejects.  Integer state only: a row's result does not depend on the rest of the launch.
+ * Refused before a launch (rc = 1): R < 0; V outside [1, 512]; k outside [1, 8] or R not a multiple of k; Lmax outside [2, 256]; t_last
+ * outside [1, Lmax); without t_ptr a t outside [1, t_last]; ld < V; tok_ld or hist_rows < 1; hist_rows < R without mol; with R > 0 a null
+ * logits, tokens or table, a pointer not 4-byte aligned or a table not 16-byte aligned.  R == 0 returns 0 without a launch. */
+#define SPMM_SYNTAX_MASKED (-1e30f)
+int spmm_smiles_mask(float* logits, float* logits2, long ld, int R, int V, const int* tokens, long tok_ld, int hist_rows, int k,
+                     const int* mol, int Lmax, int t, const int* t_ptr, int t_off, int t_last, const int* table, int* state_out,
+                     spmm_stream_t stream);
+
 /* Prefill of the decoder's self-attention cache (csrc/prefill.hip): the keys and values of E whole prefixes, computed by one packed pass,
  * moved into the head-major caches of spmm_decode_attn -- keys and values of a layer in ONE launch.
  * Source: K, V bf16 token-major rows with row stride ld elements, head h at column h*64 -- the K and V column blocks of the fused Q|K|V

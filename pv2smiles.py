@@ -6,12 +6,20 @@ stochastic k-beam search with k = 2, any subset of the 53 properties left unspec
   python pv2smiles.py --synthetic --tiny --n_generate 8 --seed 1                          (no data files: seeded weights, PV and vocabulary)
   python pv2smiles.py ... --prefix c1ccccc1                                               (every molecule starts with this SMILES fragment)
   python pv2smiles.py ... --guidance 2 --temperature 0.8 --top_k 40 --top_p 0.95          (the distribution the samples are drawn from)
+  python pv2smiles.py ... --syntax                                                        (only well-formed SMILES strings are generated)
 
 --guidance w is classifier-free guidance between the requested condition and the same decoder with every property masked,
 log p~ = log p_u + w (log p_c - log p_u): 1 (default) is the conditioned model alone, w > 1 pushes the samples towards the requested
 properties, 0 is the unconditional model.  --temperature divides the guided logits, --top_k keeps the K most probable tokens (0: all; at
 least --k), --top_p the smallest set of them whose probability reaches p (1: all).  Order: guidance, temperature, top-k, then top-p on
 the renormalised distribution; at least --k tokens always stay.  With all four at their defaults the run is the one without them.
+
+--syntax constrains every position to the tokens that can follow the beam's own history in a well-formed SMILES string that still ends
+inside --max_steps (spmm_amd/smiles_syntax.py): balanced parentheses, paired ring-bond digits, closed bracket atoms, no trailing bond or
+dot, a non-empty molecule.  Syntax only: element symbols, valence and aromaticity are not checked, two-digit ring labels (%nn) are never
+generated, and a ring closed on the atom that opened it (C11) passes.  Off by default; with a --prefix that is not the beginning of such a
+string, or cannot be closed in --max_steps tokens, the run stops before anything is decoded.  `well-formed: n / N` (the same automaton
+over the N strings written, without RDKit) is reported with and without the flag.
 
 What differs from the reference, on purpose: the seed is a flag (the reference draws one at random) and the same seed gives the same
 molecules whatever `--chunk` is; all samples of a chunk are decoded together against a K/V cache (spmm_amd.decode.generate_with_property);
@@ -91,6 +99,8 @@ def report(samples, smiles, prop_input, prop_mask, norm, names):
     print(f"samples: {n}")
     print(f"without a final hypothesis: {none}")
     print(f"uniqueness (strings): {len(set(done)) / max(len(done), 1):.4f}")
+    from spmm_amd.smiles_syntax import well_formed
+    print(f"well-formed: {sum(1 for s in done if well_formed(s))} / {len(done)}")           # (syntax only; of the molecules that were finished)
     try:
         from rdkit import Chem
         from rdkit.Chem import Descriptors
@@ -171,15 +181,28 @@ def main(args):
             prop_input, prop_mask = torch.zeros(N_PROPS), torch.ones(N_PROPS)
     model.eval()
     pv = prop_input if norm is None or args.synthetic else (prop_input - norm[0]) / norm[1]
+    syntax = None
+    if args.syntax:
+        try:
+            syntax = decode.syntax_table(model, True)      # (the vocabulary check, with a clear message, before anything is decoded)
+        except ValueError as e:
+            raise SystemExit(f"pv2smiles.py --syntax: {str(e).removeprefix('syntax: ')}")
+        print("syntax: every position is constrained to well-formed SMILES (syntax only: no elements, valence, aromaticity, %nn)")
     print(f"PV-to-SMILES generation in {'stochastic' if args.stochastic else 'deterministic'} manner with k={args.k}, seed {args.seed}...")
     prefix = prefix_ids(tokenizer, args.prefix) if args.prefix else None
     if warp is not None:
         print(f"sampling: guidance {warp['guidance']:g}, temperature {warp['temperature']:g}, top_k {warp['top_k']}, top_p {warp['top_p']:g}")
     if prefix is not None:
         print(f"prefix: {args.prefix!r} ({len(prefix)} tokens with [CLS]); every molecule starts with it")
-    samples = decode.generate_with_property(model, pv.to(device), args.n_generate, prop_mask.to(device), k=args.k, stochastic=args.stochastic,
-                                            seed=args.seed, max_steps=args.max_steps, chunk=args.chunk or None, prefix=prefix,
-                                            guidance=args.guidance, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
+    try:
+        samples = decode.generate_with_property(model, pv.to(device), args.n_generate, prop_mask.to(device), k=args.k, stochastic=args.stochastic,
+                                                seed=args.seed, max_steps=args.max_steps, chunk=args.chunk or None, prefix=prefix,
+                                                guidance=args.guidance, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+                                                syntax=syntax)
+    except ValueError as e:
+        if syntax is None or not str(e).startswith("syntax:"):
+            raise
+        raise SystemExit(f"pv2smiles.py --syntax: {str(e).removeprefix('syntax: ')}")
     smiles = [tokenizer.decode(s) for s in samples]
     with open(args.output, "w") as f:
         for s in smiles:
@@ -216,6 +239,8 @@ def parse_args(argv=None):
     p.add_argument("--temperature", default=1.0, type=float, help="divides the (guided) logits; > 0")
     p.add_argument("--top_k", default=0, type=int, help="keep the K most probable tokens (0: all; not below --k, which are always kept)")
     p.add_argument("--top_p", default=1.0, type=float, help="nucleus: keep the most probable tokens until their probability reaches p, in (0, 1] (1: all)")
+    p.add_argument("--syntax", action="store_true", help="generate well-formed SMILES strings only (syntax: parentheses, ring bonds, bracket atoms, "
+                   "bonds; not elements, valence or aromaticity)")
     p.add_argument("--synthetic", action="store_true", help="no data files: seeded weights, property vector and vocabulary")
     p.add_argument("--tiny", action="store_true", help="2-layer / 128-d encoders (configs/config_bert_tiny.json)")
     return p.parse_args(argv)

@@ -19,12 +19,13 @@ GRAPH_BELOW_ROWS = 200          # measured break-even of graph=True, not a switc
 #                                 chain of ~130 dependent kernels (1.95 ms at 100 rows, 2.2 at 1 000, 3.6 at 5 000) and replay gains 7 % at 100 rows, 2 % at
 #                                 250, nothing from 500 on -- and a replayed graph has a fixed batch: no compaction of finished molecules
 last_run: dict = {}             # what the last eager beam_search_batched did: molecules, compactions, final_batch, positions, prefix_tokens, prefill,
-#                                 guidance, temperature, top_k, top_p, baseline_rows (0, or the N*k rows of the all-masked branch)
+#                                 guidance, temperature, top_k, top_p, baseline_rows (0, or the N*k rows of the all-masked branch), syntax (bool),
+#                                 dropped_masked (finals a constrained search dropped: they went through a masked token)
 COMPACT_BELOW = 0.75            # the batch is re-gathered once at most this share of its molecules is still live
 FUSED_BEAM_STEP = True          # beam bookkeeping of a position as one HIP launch (spmm_beam_step); False: the tensor-op form (BeamBook.update)
 GUMBEL_SALT = 0x50563253        # call-site salt of the sampled search's noise ("PV2S"; dropout and negative sampling use small integers)
 last_generate: dict = {}        # what the last generate_with_property did: samples, no_final, chunks, prefix_tokens, guidance, temperature, top_k, top_p,
-#                                 baseline_rows (of the last chunk)
+#                                 baseline_rows (of the last chunk), syntax (bool), dropped_masked (summed over the chunks)
 
 
 def _pick(p: torch.Tensor, k: int, stochastic: bool, generator=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -160,6 +161,88 @@ def warp_logits(lc: torch.Tensor, lu: torch.Tensor | None = None, *, guidance: f
     keep_sorted = (r < min_keep) | ((r < K) & ((before < top_p) if top_p < 1.0 else torch.ones_like(before, dtype=torch.bool)))
     keep = torch.zeros_like(keep_sorted).scatter(-1, order, keep_sorted)
     return torch.where(keep, z, torch.full_like(z, -float("inf")))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Syntax-constrained search: the grammar mask on the raw next-token logits (smiles_syntax.py: grammar, cost, invariant).
+# ------------------------------------------------------------------------------------------------------------------
+SYNTAX_DROP_BELOW = -1e29       # a final at or below this score went through a masked token (the mask writes -1e30): it is not returned
+
+
+def syntax_table(model, syntax, prefix=None, max_steps: int | None = None):
+    """The `syntax` argument of the searches -> None (None / False: the search of today) or a smiles_syntax.SyntaxTable (True: built from
+    model.tokenizer's vocabulary, once per tokenizer).  ValueError when there is no tokenizer, when the vocabulary cannot pay the grammar's
+    cost one token at a time, when the table is not the model's vocabulary, and -- with max_steps -- when a prefix (check_prefix's result;
+    None: [CLS] alone) rejects or cannot be closed within max_steps tokens."""
+    if syntax is None or syntax is False:
+        return None
+    from . import smiles_syntax as SS
+    if syntax is True:
+        tok = getattr(model, "tokenizer", None)
+        if tok is None or not hasattr(tok, "itos"):
+            raise ValueError("syntax=True builds the grammar table from model.tokenizer and this model has none: set model.tokenizer, or pass a "
+                             "smiles_syntax.SyntaxTable")
+        table = getattr(tok, "_syntax_table", None)
+        if table is None or table.pieces != list(tok.itos):
+            table = tok._syntax_table = SS.SyntaxTable.from_vocab(tok.itos)
+    elif isinstance(syntax, SS.SyntaxTable):
+        table = syntax
+    else:
+        raise ValueError(f"syntax={syntax!r}: None, a bool or a smiles_syntax.SyntaxTable")
+    V = _vocab_size(model)
+    if V is not None and V != table.V:
+        raise ValueError(f"syntax: the table holds {table.V} pieces, the model's vocabulary {V}")
+    if (table.cls_id, table.sep_id) != (CLS_ID, SEP_ID):
+        raise ValueError(f"syntax: [CLS] / [SEP] at {table.cls_id} / {table.sep_id}, the search expects {CLS_ID} / {SEP_ID}")
+    if max_steps is not None:
+        rows = [[CLS_ID]] if prefix is None else sorted({tuple(r) for r in prefix.tolist()})
+        for r in rows:
+            SS.check_prefix_state(table, list(r), max_steps)
+    return table
+
+
+class SyntaxMask:
+    """The grammar mask of one constrained search: `mask(lc, lu, by=...)` strikes (smiles_syntax.MASKED, in place) the next-token logits
+    lc [rows, V] -- and lu, the guidance baseline, alike -- that cannot follow the rows' histories.  Before the book exists (`book` None)
+    the histories are the prefixes: by="pair" rows are the (condition, prefix) pairs of a prefill, by="row" the N*k beam rows; afterwards
+    they are the book's own token histories (through `book.mol` once the batch is compacted), kept current by the beam step.
+    kernel=True: one launch (ops.smiles_mask); else smiles_syntax.allowed per row on the host -- slow and correct: whole-prefix decoders,
+    the tensor-op bookkeeping, shapes the kernel does not take."""
+
+    def __init__(self, table, k: int, P: int, max_steps: int, device, kernel: bool):
+        self.table, self.k, self.P, self.t_last, self.Lmax = table, k, P, P + max_steps, P + max_steps + 2
+        self.device, self.kernel, self.book = device, bool(kernel), None
+        self.dev_table = torch.from_numpy(table.packed).to(device) if kernel else None
+        self.pair_hist = self.row_hist = None
+
+    def start(self, prefix: torch.Tensor | None, pom, N: int):
+        """prefix: int64 [Npairs, P] on the host (None: [CLS] alone); pom [N]: the pair of every molecule."""
+        if prefix is None:
+            self.row_hist = torch.full((N * self.k, 1), CLS_ID, dtype=torch.int32)
+        else:
+            self.pair_hist = prefix.to(torch.int32).contiguous()
+            self.row_hist = self.pair_hist[torch.as_tensor(pom).to(torch.int64)].repeat_interleave(self.k, dim=0).contiguous()
+        if self.kernel:
+            self.row_hist = self.row_hist.to(self.device)
+            self.pair_hist = None if self.pair_hist is None else self.pair_hist.to(self.device)
+
+    def __call__(self, lc: torch.Tensor, lu: torch.Tensor | None = None, by: str = "row"):
+        if self.book is None:
+            hist, t, k, mol = (self.pair_hist if by == "pair" else self.row_hist), self.P, 1, None
+        else:
+            hist, t, k, mol = self.book.tokens, self.book.t, self.k, self.book.mol
+        if lc.shape[-1] != self.table.V:
+            raise ValueError(f"syntax: the table holds {self.table.V} pieces, the logits {lc.shape[-1]}")
+        if self.kernel:
+            ops.smiles_mask(lc, hist, self.dev_table, t=t, t_last=self.t_last, k=k, mol=mol, Lmax=self.Lmax, logits2=lu)
+            return
+        from . import smiles_syntax as SS
+        rows = hist.reshape(-1, hist.shape[-1])[:, :t].cpu().tolist()
+        assert len(rows) == lc.shape[0] and mol is None, (len(rows), lc.shape)
+        keep = torch.from_numpy(np.stack([SS.allowed(self.table, r, self.t_last) for r in rows])).to(lc.device)
+        lc.masked_fill_(~keep, SS.MASKED)
+        if lu is not None:
+            lu.masked_fill_(~keep, SS.MASKED)
 
 
 @torch.no_grad()
@@ -594,11 +677,14 @@ class GuidedDecoder(CachedDecoder):
         self.R0 = self.R // 2 if self.guided else self.R                  # beam rows of the search before any compaction
         self.fused_warp = bool(FUSED_BEAM_STEP and k <= 8 and self.c.vocab_size <= 512)
         self.warp_info = dict(self.warp, baseline_rows=self.R0 if self.guided else 0)
+        self.premask = None                                               # a constrained search's SyntaxMask: on the raw logits, before the warp
 
-    def _warped(self, logits: torch.Tensor, n: int) -> torch.Tensor:
+    def _warped(self, logits: torch.Tensor, n: int, by: str = "row") -> torch.Tensor:
         """logits fp32 [2n, V] (guided: conditioned rows, then their baseline twins) or [n, V] -> warped [n, V], in place where the kernel runs."""
         w = self.warp
         lc, lu = logits[:n], (logits[n:] if self.guided else None)
+        if self.premask is not None:                                      # both halves alike: masking lc alone would be wrong for w <= 0
+            self.premask(lc, lu, by=by)
         if self.fused_warp:
             return ops.logit_warp(lc, lu, w=w["guidance"], temperature=w["temperature"], top_k=w["top_k"], top_p=w["top_p"], min_keep=self.k)
         return warp_logits(lc, lu, guidance=w["guidance"], temperature=w["temperature"], top_k=w["top_k"], top_p=w["top_p"], min_keep=self.k)
@@ -662,13 +748,18 @@ class GuidedDecoder(CachedDecoder):
         n_pairs = prefix_ids.shape[0]
         if by_steps:                                                      # the stepping twin: this class's own (two-half, warped) step
             rows = prefix_ids.detach().cpu().to(torch.int64)[pom].repeat_interleave(k, dim=0).to(self.device)
-            for j in range(rows.shape[1]):
-                logits = self.step(rows[:, j].contiguous(), j)
+            premask = self.premask                                        # (the mask belongs to the last position's logits alone)
+            try:
+                for j in range(rows.shape[1]):
+                    self.premask = premask if j == rows.shape[1] - 1 else None
+                    logits = self.step(rows[:, j].contiguous(), j)
+            finally:
+                self.premask = premask
             return logits[dst.to(self.device).long()]
         if not self.guided:
-            return self._warped(super().prefill(prefix_ids, pom), n_pairs)
+            return self._warped(super().prefill(prefix_ids, pom), n_pairs, by="pair")
         logits = super().prefill(torch.cat([prefix_ids, prefix_ids], dim=0), torch.cat([pom, pom + n_pairs]))
-        return self._warped(logits, n_pairs)
+        return self._warped(logits, n_pairs, by="pair")
 
 
 class GuidedRecompute:
@@ -684,9 +775,12 @@ class GuidedRecompute:
         self.cond = RecomputeDecoder(model, prop_embeds, k, Lmax)
         self.base = None if base_embeds is None else RecomputeDecoder(model, base_embeds[:1].expand(prop_embeds.shape[0], -1, -1), k, Lmax)
         self.warp_info = dict(self.warp, baseline_rows=0 if self.base is None else prop_embeds.shape[0] * k)
+        self.premask = None                                               # as GuidedDecoder's
 
-    def _warped(self, lc, lu):
+    def _warped(self, lc, lu, by: str = "row"):
         w = self.warp
+        if self.premask is not None:
+            self.premask(lc, lu, by=by)
         return warp_logits(lc.float(), None if lu is None else lu.float(), guidance=w["guidance"], temperature=w["temperature"], top_k=w["top_k"],
                            top_p=w["top_p"], min_keep=self.k)
 
@@ -694,7 +788,8 @@ class GuidedRecompute:
         return self._warped(self.cond.step(ids, t), None if self.base is None else self.base.step(ids, t))
 
     def prefill(self, prefix_ids: torch.Tensor, pair_of_molecule, by_steps: bool = False) -> torch.Tensor:
-        return self._warped(self.cond.prefill(prefix_ids, pair_of_molecule), None if self.base is None else self.base.prefill(prefix_ids, pair_of_molecule))
+        return self._warped(self.cond.prefill(prefix_ids, pair_of_molecule), None if self.base is None else self.base.prefill(prefix_ids, pair_of_molecule),
+                            by="pair")
 
     def reorder(self, parent: torch.Tensor, t: int):
         self.cond.reorder(parent, t)
@@ -750,7 +845,7 @@ def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int =
                         sync_every: int = 4, prop_mask: torch.Tensor | None = None, stochastic: bool = False,
                         generator=None, graph: bool | None = None, compact: bool = True, seed: int | None = None,
                         mol_base: int = 0, prefix=None, prefill: bool = True, guidance: float = 1.0, temperature: float = 1.0, top_k: int = 0,
-                        top_p: float = 1.0) -> List[List[Tuple[float, List[int]]]]:
+                        top_p: float = 1.0, syntax=None) -> List[List[Tuple[float, List[int]]]]:
     """The reference's beam search for N molecules at once (props [N,53]); result[n] is what the one-molecule search
     (oracle/decode_oracle.py::beam_search) returns for props[n].
     cached=True (default on the HIP model) decodes one token per step against the K/V cache; cached=False re-runs the prefix
@@ -785,11 +880,21 @@ def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int =
     renormalised over the kept tokens.  The seeded draws stay keyed by (seed, global molecule, absolute position, beam, token).
     ValueError before anything runs for temperature <= 0, top_p outside (0, 1], top_k < 0 or in [1, k), a non-finite guidance.  With any
     of the four set the search stays eager whatever `graph` says; with all four at their defaults (guidance = 1 never builds the
-    baseline) it is the search without them, launch for launch.  last_run records the four and baseline_rows (0 or N*k)."""
+    baseline) it is the search without them, launch for launch.  last_run records the four and baseline_rows (0 or N*k).
+    syntax: None / False -- the search as it is, launch for launch -- or True (the grammar table is built from model.tokenizer) or a
+    smiles_syntax.SyntaxTable: every position, the first pick included, chooses among the tokens that can follow the beam's own history in
+    a well-formed SMILES string that still ends by the last position (smiles_syntax.py: grammar, cost, invariant; SYNTAX ONLY -- no
+    elements, valence, aromaticity, `%nn`).  The mask goes on the raw logits before guidance and truncation read them (on both halves of
+    a guided decoder); one launch per position (ops.smiles_mask) wherever the one-launch beam step runs, smiles_syntax.allowed on the
+    host elsewhere.  A beam with fewer than k allowed tokens takes masked ones too: those hypotheses score <= -1e29 and are not
+    returned (last_run["dropped_masked"]); the scores returned are renormalised over the allowed (and kept) tokens.  ValueError before
+    anything runs when the model has no tokenizer, the vocabulary lacks a closing piece, or the prefix rejects or cannot be closed in
+    max_steps tokens.  A constrained search stays eager whatever `graph` says."""
     warp = check_warp(guidance, temperature, top_k, top_p, k)
     if cached is None:
         cached = hasattr(model, "engine")
     prefix = check_prefix(prefix, props.shape[0], _vocab_size(model), max_steps)
+    syntax = syntax_table(model, syntax, prefix, max_steps)
     prop_embeds = encode_properties(model, props, prop_mask)
     if cached:
         model.engine.train_mode = False
@@ -804,7 +909,8 @@ def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int =
     if prefix is not None:
         prefix = prefix.expand(N, P)                     # one (PV, prefix) pair per molecule; equal prefixes share the unimodal layers
     return _search(model, dec, N, k=k, max_steps=max_steps, sync_every=sync_every, stochastic=stochastic, generator=generator,
-                   graph=bool(graph), compact=compact, seed=seed, mol_base=mol_base, prefix=prefix, pair_of_molecule=range(N), prefill=prefill)
+                   graph=bool(graph), compact=compact, seed=seed, mol_base=mol_base, prefix=prefix, pair_of_molecule=range(N), prefill=prefill,
+                   syntax=syntax)
 
 
 def _baseline_embeds(model, pv: torch.Tensor) -> torch.Tensor:
@@ -814,13 +920,16 @@ def _baseline_embeds(model, pv: torch.Tensor) -> torch.Tensor:
 
 
 def _advance(dec, book: BeamBook, ids: torch.Tensor, t: int, *, t_dev: torch.Tensor | None = None, noise=None, pick=None,
-             ids_out: torch.Tensor | None = None) -> torch.Tensor:
+             ids_out: torch.Tensor | None = None, premask=None) -> torch.Tensor:
     """One position of the search: the tokens `ids` at position t of every beam row -> the tokens at position t + 1, with the book and the
     decoder's ancestry brought up to date -- by the one-launch beam step (book.fused) or by pick, BeamBook.update and reorder.
     t_dev (int32 [1], device; cached decoder): the position comes from device memory in every launch and t is ignored, so the call can
     be captured once and replayed.  noise: the seeded search's source (_GumbelNoise).  pick(logits [N, k, V], noise) -> (log-probs, ids)
-    [N, k, k]: the candidates of the tensor-op form (None: the k most probable).  ids_out: static buffer that receives the result."""
+    [N, k, k]: the candidates of the tensor-op form (None: the k most probable).  ids_out: static buffer that receives the result.
+    premask: a constrained search's SyntaxMask for a decoder that returns raw logits (a guided one applies it itself, before its warp)."""
     logits = dec.step(ids, t) if t_dev is None else dec.step(ids, t, t_dev=t_dev)
+    if premask is not None:
+        premask(logits)
     noise = None if noise is None else noise(t, book.mol)
     if book.fused:
         anc, rowmap = dec.search_tables()
@@ -836,44 +945,69 @@ def _advance(dec, book: BeamBook, ids: torch.Tensor, t: int, *, t_dev: torch.Ten
 
 def _search(model, dec, N: int, *, k: int, max_steps: int, sync_every: int = 4, stochastic: bool = False, generator=None, graph: bool = False,
             compact: bool = True, seed: int | None = None, mol_base: int = 0, need: int | None = None, prefix: torch.Tensor | None = None,
-            pair_of_molecule=None, prefill: bool = True):
+            pair_of_molecule=None, prefill: bool = True, syntax=None):
     """beam_search_batched behind the decoder's construction (generate_with_property builds its decoders from one encoded PV).
     need: finals that end a molecule's search (BeamBook; None: k).  prefix (check_prefix's result, int64 [Npairs, P], P >= 2) with
     pair_of_molecule [N]: molecule n starts from prefix[pair_of_molecule[n]] (CachedDecoder.prefill; prefill=False: its stepping twin);
-    the decoder was built for Lmax = P + max_steps + 2."""
+    the decoder was built for Lmax = P + max_steps + 2.  syntax: beam_search_batched's (the table, True, or None / False)."""
     last_run.clear()
     cached, dev = isinstance(dec, CachedDecoder), dec.device
     P = 1 if prefix is None else int(prefix.shape[1])
     if prefix is not None and P + max_steps + 2 > DECODE_MAXL:
         raise ValueError(f"P + max_steps + 2 = {P} + {max_steps} + 2 exceeds the {DECODE_MAXL} positions the decode kernels hold")
-    if prefix is None:
-        ids = torch.full((N * k,), CLS_ID, dtype=torch.long, device=dev)
-        logits = dec.step(ids, 0).view(N, k, -1)[:, 0].float()              # all k rows hold the same [CLS] prefix
-    else:
-        pom = torch.as_tensor(pair_of_molecule).to(torch.int64)
-        logits = dec.prefill(prefix, pom, by_steps=not prefill)[pom.to(dev)].float()      # [N, V]: the k rows of a molecule hold the same prefix
-        prefix = prefix[pom]
-    Lmax, V = P + max_steps + 2, logits.shape[-1]
+    Lmax = P + max_steps + 2
     seeded = bool(stochastic and seed is not None)
     # one launch per position for the beam bookkeeping (csrc/decode.hip::beam_step_kernel: k <= 8 beams, vocabulary <= 512, histories <= 256
-    # tokens -- the tensor-op bookkeeping serves everything else); spmm_gumbel_noise accepts the same shapes
+    # tokens -- the tensor-op bookkeeping serves everything else); spmm_gumbel_noise and spmm_smiles_mask accept the same shapes
     fits = bool(cached and k <= 8 and model.cfg.text.vocab_size <= 512 and Lmax <= 256)
-    book = BeamBook(N, k, max_steps, dev, fused=bool(fits and FUSED_BEAM_STEP and (seeded or not stochastic)), need=need, prefix=prefix)
+    fused = bool(fits and FUSED_BEAM_STEP and (seeded or not stochastic))
+    table = syntax_table(model, syntax, prefix, max_steps)
+    mask = None
+    if table is not None:
+        mask = SyntaxMask(table, k, P, max_steps, dev, kernel=fused)
+        mask.start(prefix, pair_of_molecule, N)
+    # the mask sits on the raw logits: a guided decoder applies it itself, in front of its warp; for the others this function does
+    if hasattr(dec, "premask"):
+        dec.premask, own_mask = mask, None
+    else:
+        own_mask = mask
+    if prefix is None:
+        ids = torch.full((N * k,), CLS_ID, dtype=torch.long, device=dev)
+        logits = dec.step(ids, 0)
+        if own_mask is not None:
+            own_mask(logits, by="row")
+        logits = logits.view(N, k, -1)[:, 0].float()                        # all k rows hold the same [CLS] prefix
+    else:
+        pom = torch.as_tensor(pair_of_molecule).to(torch.int64)
+        logits = dec.prefill(prefix, pom, by_steps=not prefill)
+        if own_mask is not None:
+            own_mask(logits, by="pair")
+        logits = logits[pom.to(dev)].float()             # [N, V]: the k rows of a molecule hold the same prefix
+        prefix = prefix[pom]
+    V = logits.shape[-1]
+    book = BeamBook(N, k, max_steps, dev, fused=fused, need=need, prefix=prefix)
     noise_at = _GumbelNoise(seed, mol_base, N, k, V, Lmax, dev, on_device=fits) if seeded else None
 
     def pick(logits, noise):
+        if stochastic and not seeded and mask is not None:
+            # torch.multinomial cannot draw k tokens from fewer than k non-zero probabilities; Gumbel-top-k from the generator's uniforms is
+            # the same distribution and ranks the masked tokens last
+            u = torch.rand(logits.shape, generator=generator, device=logits.device if generator is None else generator.device)
+            return _pick_seeded(logits, -torch.log(-torch.log(u.clamp(1e-12, 1 - 1e-7))).to(logits.device), k)
         return _pick_seeded(logits, noise, k) if seeded else _pick(torch.softmax(logits, dim=-1), k, stochastic, generator)
 
     values, indices = pick(logits, noise_at(P - 1).view(N, k, -1)[:, 0] if seeded else None)      # (noise keyed by the absolute position)
     book.first(values, indices)
     ids = indices.reshape(N * k)
-    if graph and cached and not stochastic and prefix is None and not hasattr(dec, "warp_info"):
+    if mask is not None:
+        mask.book = book                                 # from here on the histories are the book's
+    if graph and cached and not stochastic and prefix is None and not hasattr(dec, "warp_info") and mask is None:
         return _decode_graphed(dec, book, ids, max_steps, sync_every)
     n_cur = N
     last_run.update(molecules=N, compactions=0, final_batch=N, positions=0, prefix_tokens=P, prefill=bool(prefix is not None and prefill),
-                    **getattr(dec, "warp_info", dict(NO_WARP, baseline_rows=0)))
+                    **getattr(dec, "warp_info", dict(NO_WARP, baseline_rows=0)), syntax=mask is not None, dropped_masked=0)
     for s in range(max_steps):
-        ids = _advance(dec, book, ids, P + s, noise=noise_at, pick=pick)
+        ids = _advance(dec, book, ids, P + s, noise=noise_at, pick=pick, premask=own_mask)
         last_run["positions"] = s + 1
         if s % sync_every != sync_every - 1:
             continue
@@ -894,13 +1028,20 @@ def _search(model, dec, N: int, *, k: int, max_steps: int, sync_every: int = 4, 
             n_cur = int(keep.numel())
             last_run["compactions"] += 1
             last_run["final_batch"] = n_cur
-    return book.results()
+    res = book.results()
+    if mask is not None:
+        # a hypothesis that went through a masked token carries <= -1e30 in its score; one that continued a struck-out [SEP] candidate (a
+        # molecule with fewer than k live candidates) holds [SEP] inside -- its history rejects, so every token after it was masked alike
+        kept = [[h for h in finals if h[0] > SYNTAX_DROP_BELOW and SEP_ID not in h[1][1:-1]] for finals in res]
+        last_run["dropped_masked"] = sum(len(a) - len(b) for a, b in zip(res, kept))
+        res = kept
+    return res
 
 
 @torch.no_grad()
 def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: torch.Tensor | None = None, k: int = 2, stochastic: bool = True,
                            seed: int = 0, max_steps: int = 100, chunk: int | None = None, prefix=None, prefill: bool = True, guidance: float = 1.0,
-                           temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> List[List[int]]:
+                           temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, syntax=None) -> List[List[int]]:
     """`generate_with_property` of d_pv2smiles_single.py:54-111: n_sample molecules from ONE (normalised) property vector pv [53], with the
     properties of prop_mask ([53], 1 = unspecified) replaced by the mask token.  Returns one token-id list per sample ([CLS] ... [SEP]; empty
     when the search of that sample finished nothing -- counted in last_generate["no_final"]).
@@ -915,10 +1056,13 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
     guidance, temperature, top_k, top_p: beam_search_batched's, with the same checks and defaults (all at their defaults: the run without
     them).  The guidance baseline is this PV with every property masked; it is encoded once, and its cross-attention keys | values are
     projected once per run next to the condition's (`xkv_once`) -- a chunk of n samples is 2 conditions x n molecules in one decoder.  The
-    samples still do not depend on the chunking.  last_generate records the four and baseline_rows."""
+    samples still do not depend on the chunking.  last_generate records the four and baseline_rows.
+    syntax: beam_search_batched's -- every sample returned is a well-formed SMILES string (syntax only), whatever the chunking: the mask
+    of a row is a function of the row's own history.  last_generate records `syntax` and `dropped_masked`."""
     warp = check_warp(guidance, temperature, top_k, top_p, k)
     cached = hasattr(model, "engine")
     prefix = check_prefix(prefix, 1, _vocab_size(model), max_steps)
+    syntax = syntax_table(model, syntax, prefix, max_steps)
     P = 1 if prefix is None else prefix.shape[1]
     prop_embeds = encode_properties(model, pv.reshape(1, -1), None if prop_mask is None else prop_mask.reshape(1, -1))
     if cached:
@@ -926,7 +1070,7 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
     chunk = n_sample if not chunk else min(int(chunk), n_sample)
     rng = random.Random(seed)
     out: List[List[int]] = []
-    xkv, none = None, 0
+    xkv, none, dropped = None, 0, 0
     base_embeds = _baseline_embeds(model, pv) if warp is not None and warp["guidance"] != 1.0 else None
     for base in range(0, n_sample, chunk):
         n = min(chunk, n_sample - base)
@@ -942,7 +1086,8 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
         else:
             dec = RecomputeDecoder(model, prop_embeds.expand(n, -1, -1), k, P + max_steps + 2)
         res = _search(model, dec, n, k=k, max_steps=max_steps, stochastic=stochastic, seed=seed if stochastic else None, mol_base=base,
-                      prefix=prefix, pair_of_molecule=[0] * n, prefill=prefill)
+                      prefix=prefix, pair_of_molecule=[0] * n, prefill=prefill, syntax=syntax)
+        dropped += last_run.get("dropped_masked", 0)
         for finals in res:
             if not finals:
                 none += 1
@@ -951,7 +1096,8 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
                 out.append(finals[rng.randrange(len(finals)) if stochastic else 0][1])
     last_generate.clear()
     last_generate.update(samples=n_sample, no_final=none, chunks=(n_sample + chunk - 1) // chunk, prefix_tokens=P,
-                         **{f: last_run.get(f, v) for f, v in dict(NO_WARP, baseline_rows=0).items()})
+                         **{f: last_run.get(f, v) for f, v in dict(NO_WARP, baseline_rows=0).items()}, syntax=syntax is not None,
+                         dropped_masked=dropped)
     return out
 
 

@@ -642,6 +642,36 @@ def logit_warp(lc, lu=None, *, w=1.0, temperature=1.0, top_k=0, top_p=1.0, min_k
     return out
 
 
+SYNTAX_MASKED = -1e30    # SPMM_SYNTAX_MASKED (include/spmm_hip.h)
+
+
+def smiles_mask(logits, tokens, table, *, t=0, t_last, k=1, mol=None, Lmax=None, logits2=None, t_ptr=None, t_off=0, state_out=None):
+    """The grammar mask of the syntax-constrained search in one launch (csrc/syntax.hip, spmm_smiles_mask; the host reference is
+    smiles_syntax.allowed): logits fp32 [R, V] (and logits2, same shape and row stride) get SYNTAX_MASKED, in place, wherever the token
+    cannot follow the row's history; the other entries keep their bits.  tokens: int32 histories [rows, >= t] (a strided 2-D view is
+    fine, e.g. book.tokens[:, 0]) or [N, k, Lmax]; beam row i reads history row (mol[i // k] if mol is given else i // k) * k + i % k.
+    t: tokens held by every row (t_ptr, int32 [1] on the device: *t_ptr + t_off); t_last: the last position the search can write;
+    table: smiles_syntax.SyntaxTable.packed on the device (int32 [V, 4]); state_out: int32 [R, 4] <- (q, depth, rings, cost)."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and (logits.stride(1) == 1 or logits.shape[1] == 1)
+    R, V = logits.shape
+    if logits2 is not None:
+        assert logits2.dtype == torch.float32 and logits2.shape == logits.shape and logits2.device == logits.device
+        assert (R <= 1 or logits2.stride(0) == logits.stride(0)) and (logits2.stride(1) == 1 or V == 1)
+    assert tokens.dtype == torch.int32 and tokens.dim() in (2, 3) and tokens.stride(-1) == 1
+    if tokens.dim() == 3:
+        assert tokens.is_contiguous() and tokens.shape[1] == k
+        tokens = tokens.view(-1, tokens.shape[2])
+    if Lmax is None:
+        Lmax = tokens.shape[1]
+    assert tokens.shape[1] >= (t if t_ptr is None else t_last), (tokens.shape, t, t_last)      # (the kernel reads positions < t <= t_last)
+    assert table.dtype == torch.int32 and tuple(table.shape) == (V, 4) and table.is_contiguous() and table.device == logits.device
+    assert mol is None or (mol.dtype == torch.int32 and mol.is_contiguous() and mol.numel() * k == R)
+    assert state_out is None or (state_out.dtype == torch.int32 and tuple(state_out.shape) == (R, 4) and state_out.is_contiguous())
+    _call("spmm_smiles_mask", _p(logits), _p(logits2), logits.stride(0), R, V, _p(tokens), tokens.stride(0), tokens.shape[0], int(k), _p(mol),
+          int(Lmax), int(t), _p(t_ptr), int(t_off), int(t_last), _p(table), _p(state_out), _st())
+    return logits
+
+
 def kv_prefill(K, V, row0, length, dst_row, Kc, Vc):
     """Whole prefixes into the decoder's self-attention cache (csrc/prefill.hip, spmm_kv_prefill): K / V bf16 [rows, nH*64] views of
     token-major rows with one row stride (the K and V column blocks of a fused Q|K|V projection); Kc / Vc bf16 [R, nH, Lmax, 64]
