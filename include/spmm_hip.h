@@ -137,6 +137,27 @@ int spmm_xattn_fwd(const void* Q, long ldq, const void* K, long ldk, const void*
                    void* Y, long ldy, void* Z, long ldz, float* mean, float* rstd, void* CTX, long ldc, float* LSE,
                    int nseq, int nH, int Lq, int Lkv, float attn_dropout_p, uint64_t salt_a, float hidden_dropout_p,
                    uint64_t salt_h, const uint64_t* seed_ptr, long row_base, spmm_stream_t stream);
+/* Cross-attention probabilities as an output (csrc/attnmap.hip), one launch:
+ *   P[s, h, q, j] = softmax_j(Q_h[q] . K_h[j] / 8 + mask),   P_mean[row(s, q), j] = (1 / nH) sum_h P[s, h, q, j]
+ * Replaces BertSelfAttention.forward xbert.py:305-340 up to `attention_probs` (cross instantiation :285-290, encoder mask of
+ * invert_attention_mask :1038-1043), without the dropout of :344: the probabilities themselves, which spmm_attn_fwd and spmm_xattn_fwd
+ * never hold outside registers.  The mask is the cross mask of spmm_attn_fwd(is_cross=1): key j is masked if kmask[s, j] == 0 (kmask:
+ * [nseq, Lkv], null = all ones) or j >= kv_len[source].  Q, K: the bf16 projections (head h at column h*64, head_dim 64, any nH in 1..16),
+ * row strides ldq, ldk in elements (multiples of 8).  kv_seq, q_row0/q_len, kv_row0/kv_len: exactly as for spmm_attn_fwd; Lq, Lkv <= 256.
+ * P_mean, P_heads (either may be null, not both): fp32, indexed by QUERY ROW like Q, row stride ldp >= Lkv, columns 0 .. Lkv-1; head h of
+ * P_heads starts at P_heads + h * head_stride.  Columns of masked keys are written as exactly 0.0f; columns [Lkv, ldp) and rows that
+ * belong to no sequence are not written; a query row whose keys are all masked gets zeros.  Scores on MFMAs from the bf16 inputs with fp32
+ * accumulation; maximum, exponential, row sum and division in fp32; nothing is rounded to bf16.  The heads are summed in ascending order
+ * in registers by the workgroup that owns the row (no atomics).  A sequence's rows of both outputs have the same bits wherever it sits in
+ * the launch, whatever the other sequences are, for any launch Lkv >= its source length, and whether its source is reached through kv_seq
+ * or a private copy.
+ * Refused before a launch (rc = 1): a null Q or K; both outputs null; Q or K not 16-byte aligned (outputs and int arrays: 4 bytes); nH
+ * outside [1, 16]; ldq or ldk < nH*64 or not a multiple of 8; Lq or Lkv outside [1, 256]; ldp < Lkv; nseq < 0; q_row0/q_len or
+ * kv_row0/kv_len not given together; with P_heads and nH > 1 a head_stride < ldp.  nseq == 0 returns 0 without a launch. */
+int spmm_attn_probs(const void* Q, long ldq, const void* K, long ldk, const int* kmask, const int* kv_seq,
+                    const int* q_row0, const int* q_len, const int* kv_row0, const int* kv_len,
+                    float* P_mean, float* P_heads, long ldp, long head_stride,
+                    int nseq, int nH, int Lq, int Lkv, spmm_stream_t stream);
 /* out[u] = sum over k in [start[u], start[u+1]) of src[list[k]]  (rows of W bf16 elements, fp32 accumulation, fixed order).
  * Folds the per-query-sequence dK/dV of a cross-attention whose sequences share key/value sources (kv_seq) back onto the
  * unique sources before the K/V weight- and data-gradient GEMMs. */

@@ -514,9 +514,10 @@ class Engine:
         self._wgrad(dx, A, P.g(op + "dense.weight"), md=md)
         return dz, dx
 
-    def _attn_block_fwd(self, pfx, c, X, groups, save, cross, X32=None, kv_tap=None):
+    def _attn_block_fwd(self, pfx, c, X, groups, save, cross, X32=None, kv_tap=None, xattn_tap=None):
         """BertAttention.forward xbert.py:401-422 on a token batch.  cross=True uses the groups' key/value sources.
         kv_tap (self-attention only): called with the fused Q|K|V projection [M, 3H] right after it is formed (`stack_fwd`).
+        xattn_tap (cross-attention only): called per group with its projected query rows and its source's keys (`stack_fwd`).
         -> (y, tape entry, fp32 twin of y or None)."""
         P, H, nH = self.P, c.hidden_size, c.num_attention_heads
         # Every form of the block draws its salts here, in one order (every group's attention salt, then the hidden one): the composite of
@@ -532,6 +533,11 @@ class Engine:
             done = {id(g.src): g.src.proj[pfx] for g in groups if g.src is not None and g.src.proj and pfx in g.src.proj}
             kv_of = functools.partial(self._xattn_kv, P.fused(pfx + ".self.", ("key", "value"), "weight"),
                                       P.fused(pfx + ".self.", ("key", "value"), "bias", what="w"), done)
+            if xattn_tap is not None:
+                # views of what both forms of the block read below: no copy, no salt, no launch.  (kv_of caches per source, so the
+                # block's own kv_of(g) returns the very tensor the tap saw.)
+                for gi, g in enumerate(groups):
+                    xattn_tap(gi, g, Qc[g.rows], kv_of(g)[:, :H])
             fx = self.opt.fused_xattn
             fused = ((fx is True or fx == "all" or (fx == "nograd" and not save)) and not self._xattn_off and X32 is None
                      and groups.rows_dev is None and all(ops.xattn_supported(H, nH, g.L, g.Lkv) for g in groups))
@@ -720,14 +726,15 @@ class Engine:
         return dX
 
     # ------------------------------------------------------------------------------------------------- layers
-    def _layer_fwd(self, lp, c, has_cross, X, groups, save, X32=None, kv_tap=None):
+    def _layer_fwd(self, lp, c, has_cross, X, groups, save, X32=None, kv_tap=None, xattn_tap=None):
         """BertLayer.forward xbert.py:469-534.  -> (y, tape entry, fp32 twin of y or None)."""
         P, H, I, M = self.P, c.hidden_size, c.intermediate_size, X.shape[0]
         tap = {} if kv_tap is None else {"kv_tap": kv_tap}       # (without a tap the call is the one it always was: bench.py wraps this method)
         a, sv1, a32 = self._attn_block_fwd(lp + "attention", c, X, groups, save, cross=False, X32=X32, **tap)
         sv2 = None
         if has_cross:
-            a, sv2, a32 = self._attn_block_fwd(lp + "crossattention", c, a, groups, save, cross=True, X32=a32)
+            xtap = {} if xattn_tap is None else {"xattn_tap": xattn_tap}
+            a, sv2, a32 = self._attn_block_fwd(lp + "crossattention", c, a, groups, save, cross=True, X32=a32, **xtap)
         h = self._new(M, I)
         # backward needs only gelu'(pre-activation): the forward epilogue stores it (it shares the exponential with the erf) and the
         # backward epilogue is a plain multiply -- the erf / exp work of xbert.py:436's backward leaves the dgrad GEMM
@@ -752,15 +759,20 @@ class Engine:
             da = self._attn_block_bwd(lp + "crossattention", c, sv["cross"], da, groups, dkv_acc)
         return self._attn_block_bwd(lp + "attention", c, sv["att"], da, groups, None)
 
-    def stack_fwd(self, pfx, c, layers, has_cross, X, groups, save, X32=None, kv_tap=None):
+    def stack_fwd(self, pfx, c, layers, has_cross, X, groups, save, X32=None, kv_tap=None, xattn_tap=None):
         """groups: the Batch X holds.  -> (y, tape, y32).  With X32 (the fp32 twin of X: EngineOptions.resid_fp32) the residual stream runs
         in fp32 and y32 is the fp32 twin of y (None otherwise).  kv_tap(layer index, QKV [M, 3H]) is called with every layer's
         self-attention Q|K|V projection right after it is formed (decode.CachedDecoder.prefill fills its K/V cache from it); None, the
-        default, changes nothing -- no launch, no salt."""
+        default, changes nothing -- no launch, no salt.  xattn_tap(layer index, group index, group, Q rows of the group [rows, H],
+        K of its source [source rows, H]) is called once per cross-attention group of every layer that has a cross-attention block, right
+        after the group's K/V projection is available, on the composite and on the one-launch form alike (attribution.py reads the
+        attention probabilities from these views); None, the default: the calls below are the ones they always were."""
         tape = []
         for i in layers:
             tap = None if kv_tap is None else functools.partial(kv_tap, i)
-            X, sv, X32 = self._layer_fwd(f"{pfx}encoder.layer.{i}.", c, has_cross and i >= c.fusion_layer, X, groups, save, X32=X32, kv_tap=tap)
+            xtap = {} if xattn_tap is None else {"xattn_tap": functools.partial(xattn_tap, i)}
+            X, sv, X32 = self._layer_fwd(f"{pfx}encoder.layer.{i}.", c, has_cross and i >= c.fusion_layer, X, groups, save, X32=X32, kv_tap=tap,
+                                         **xtap)
             tape.append(sv)
         return X, tape, X32
 

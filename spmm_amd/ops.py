@@ -141,6 +141,34 @@ def attn_bwd(Q, K, V, O, lse, dO, dQ, dK, dV, *, nseq, nH, Lq, Lkv, kmask=None, 
                _p(dbuf), _st())
 
 
+def attn_probs(Q, K, *, nseq, nH, Lq, Lkv, kmask=None, kv_seq=None, q_row0=None, q_len=None, kv_row0=None, kv_len=None, mean=True, heads=False,
+               P_mean=None, P_heads=None):
+    """Cross-attention probabilities softmax(Q K^T / 8 + cross mask) in fp32, one launch (csrc/attnmap.hip, spmm_attn_probs).  Q, K: bf16
+    2-D views with row strides, layout arguments as attn_fwd(is_cross=True).  -> (P_mean [rows of Q, Lkv] or None, P_heads [nH, rows of
+    Q, Lkv] or None): allocated here when `mean` / `heads` ask for them and none is given.  Indexed by query row like Q; masked columns
+    are 0; rows that belong to no sequence keep what they held (zeros, when allocated here)."""
+    assert Q.dtype == BF16 and K.dtype == BF16 and Q.dim() == 2 and K.dim() == 2
+    rows = Q.shape[0]
+    if P_mean is None and mean:
+        P_mean = torch.zeros(rows, Lkv, dtype=torch.float32, device=Q.device)
+    if P_heads is None and heads:
+        P_heads = torch.zeros(nH, rows, Lkv, dtype=torch.float32, device=Q.device)
+    assert P_mean is not None or P_heads is not None, "attn_probs: nothing requested"
+    ldp = None
+    if P_mean is not None:
+        assert P_mean.dtype == torch.float32 and P_mean.dim() == 2 and P_mean.shape[0] >= rows and P_mean.shape[1] >= Lkv
+        ldp = _row_stride(P_mean)
+    hs = 0
+    if P_heads is not None:
+        assert P_heads.dtype == torch.float32 and P_heads.dim() == 3 and tuple(P_heads.shape[:2]) == (nH, rows) and P_heads.shape[2] >= Lkv
+        assert P_heads.stride(2) == 1 or P_heads.shape[2] == 1
+        assert ldp is None or ldp == P_heads.stride(1), "attn_probs: P_mean and P_heads share one row stride"
+        ldp, hs = P_heads.stride(1), P_heads.stride(0)
+    _call("spmm_attn_probs", _p(Q), _row_stride(Q), _p(K), _row_stride(K), _p(kmask), _p(kv_seq), _p(q_row0), _p(q_len), _p(kv_row0),
+          _p(kv_len), _p(P_mean), _p(P_heads), int(ldp), int(hs), int(nseq), int(nH), int(Lq), int(Lkv), _st())
+    return P_mean, P_heads
+
+
 def xattn_supported(H, nH, Lq, Lkv):
     return bool(_DRY_RUN or lib().cdll.spmm_xattn_supported(int(H), int(nH), int(Lq), int(Lkv)))
 

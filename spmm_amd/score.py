@@ -84,9 +84,10 @@ def _from_logits(logits: torch.Tensor, ids: torch.Tensor, L_out: int) -> Scores:
     return Scores(tok.sum(1), n, tok)
 
 
-def _decode_scores(eng, ct, ids_h, lens_all, pairs_h, src: KVSource, fused: bool, L_out: int, what: str) -> Scores:
+def _decode_scores(eng, ct, ids_h, lens_all, pairs_h, src: KVSource, fused: bool, L_out: int, what: str, xattn_tap=None) -> Scores:
     """The shared engine path: the causal decoder `text_encoder` over the sequences ids_h (host, PAD = 0 beyond lens_all) of the pairs,
-    pair p cross-attending sequence pairs_h[p, 0] of `src` in the fusion layers -> Scores."""
+    pair p cross-attending sequence pairs_h[p, 0] of `src` in the fusion layers -> Scores.  xattn_tap: Engine.stack_fwd's, on the fusion
+    layers (attribution.reaction_attention_maps; pair p owns lens_all[pairs_h[p, 1]] packed query rows, in pair order)."""
     dev = eng.dev
     P = pairs_h.shape[0]
     f, n = ct.fusion_layer, ct.num_hidden_layers
@@ -111,7 +112,7 @@ def _decode_scores(eng, ct, ids_h, lens_all, pairs_h, src: KVSource, fused: bool
     X = t.y.index_select(0, i64(gat))
     qrow0_d, qlen_d = i32(qrow0), i32(len_p)
     gq = Batch([Group(0, P, Lt, None, 0, q_row0=qrow0_d, q_len=qlen_d, nrows=Mt).bind(src, i32(iq), 0)])
-    y, _, _ = eng.stack_fwd(TP, ct, range(f, n), True, X, gq, False)
+    y, _, _ = eng.stack_fwd(TP, ct, range(f, n), True, X, gq, False, **({} if xattn_tap is None else {"xattn_tap": xattn_tap}))
     # ---- the tied LM head on the Mt rows; row r = position pos[r] of pair seq[r] = dense row seq[r] * Lt + pos[r] of the [P, Lt] ids
     W = max(L_out, Lt)
     lay = dict(P=P, Lt=Lt, W=W, row_of=i64(seq * Lt + pos), pos=i64(pos), dest=i64(seq * W + pos), seq_row0=qrow0_d, seq_len=qlen_d,
@@ -217,6 +218,12 @@ def score_products(model, src_ids: torch.Tensor, src_mask: torch.Tensor, prod_id
     eng = _engine(model)
     if P == 0:
         return _empty(L, eng.dev)
+    src, inv_s = _rxn_memory(model, eng, sids_h, slens, pairs_h, what)
+    return _decode_scores(eng, model.cfg.text, pids_h, plens, torch.stack([inv_s, pairs_h[:, 1]], dim=1), src, fused, L, what)
+
+
+def _rxn_memory(model, eng, sids_h, slens, pairs_h, what: str):
+    """-> (the encoded reactants of the pairs' distinct sources as a shared cross-attention source, source of every pair in it)."""
     ce, dev = model.cfg_enc, eng.dev
     ss, inv_s = torch.unique(pairs_h[:, 0], return_inverse=True)
     lens_s = slens[ss.numpy()]
@@ -227,5 +234,4 @@ def score_products(model, src_ids: torch.Tensor, src_mask: torch.Tensor, prod_id
     mask_s = (torch.arange(Ls)[None, :] < torch.from_numpy(lens_s)[:, None]).to(torch.int32)
     mem = eng.encode_text(EP, ce, sids_h[ss, :Ls].to(dev).to(torch.int32).contiguous(), mask_s.to(dev).contiguous(),
                           n_tokens=host_token_count(mask_s), what=what + ": ")
-    src = mem.source(tables=True)
-    return _decode_scores(eng, model.cfg.text, pids_h, plens, torch.stack([inv_s, pairs_h[:, 1]], dim=1), src, fused, L, what)
+    return mem.source(tables=True), inv_s
