@@ -308,6 +308,43 @@ int spmm_smiles_mask(float* logits, float* logits2, long ld, int R, int V, const
                      const int* mol, int Lmax, int t, const int* t_ptr, int t_off, int t_last, const int* table, int* state_out,
                      spmm_stream_t stream);
 
+/* One position of stochastic beam search (Kool, van Hoof, Welling 2019; csrc/sbs.hip): sequences sampled WITHOUT replacement, for G
+ * property vectors ("groups") of W slots each, in ONE launch (one workgroup per group; selection and gather share the launch because
+ * every state array has an _out twin, so no input is overwritten before it is read).
+ * logits, noise: fp32 [G*W, V], row strides ldl, ldn -- the next-token logits of every slot's row after any warp or mask, and the caller's
+ * Gumbel noise (spmm_gumbel_noise).  t (*t_ptr + t_off when t_ptr is given, clamped into [0, Lmax - 2]): the tokens every live slot
+ * holds = the position the new token lands at.
+ * State in, row r = g*W + s: phi_in[r] log-probability of the slot's hypothesis; gum_in[r] its perturbed key T (-inf, or NaN: an EMPTY
+ * slot); fin_in[r] (uchar) the hypothesis has ended; len_in[r]; tokens_in[r, Lmax] (int32); anc_in[r, anc_ld] (spmm_decode_attn's table).
+ * Candidates of a group: an empty slot none; a finished slot i exactly one -- itself: key T_i, phi_i, token [SEP] (3); a live slot i one
+ * per ALLOWED token j, allowed iff logits[i, j] > -1e29 (-inf and SPMM_SYNTAX_MASKED are not); a live slot with nothing allowed none.
+ * Arithmetic, fp32, every operation rounded on its own, a row's sums in a fixed order:
+ *     lse = log-sum-exp of l over the allowed tokens          phi_j = phi_i + (l_j - lse)          g_j = phi_j + noise[i, j]
+ *     Z = max_j g_j          v_j = T_i - g_j + log1p(-exp(g_j - Z))          key_j = T_i - max(0, v_j) - log1p(exp(-|v_j|))
+ * so the arg-max child has key = T_i exactly (log1p(-1) = -inf) and every other child a smaller one; a key that is NaN (noise that is not
+ * finite) is no candidate.  A search starts with slot 0 at phi = 0, T = 0 and every other slot empty: position 0 has no mode of its own.
+ * Selection: the W best candidates by (key descending, flat index i*V + j ascending) become slots 0 .. W-1 in that order; slots beyond the
+ * number of finite candidates become empty (gum = phi = -inf, fin = 0, len = 0, tokens 0, ids_out = 0, their own ancestry row).
+ * New slot s of parent p and token v: phi, gum = the candidate's; fin = fin_in[p] | (v == [SEP]); tokens_out[s] = tokens_in[p] with
+ * position t <- v if p was live; len = len_in[p] if p was finished, else t + 1; anc_out[row(s), j] = anc_in[row(p), j] for j < t (clamped
+ * into [0, G*W)) and row(s) for j >= t -- spmm_beam_step's convention without rowmap: cache rows never move.  ids_out[row(s)] = v, or 0
+ * for a finished or empty slot: a finished slot's row keeps being stepped with token 0; nothing descends from it (its only candidate is
+ * itself, and a child's ancestry below t is its parent's), so what that row writes into its own cache row is never read.
+ * parent_out (optional) [G*W]: p (s for an empty slot).  open_out[g] (int32, plain store): live, unfinished slots after the step.
+ * ws: 2*G*W*V 32-bit words of scratch, 8-byte aligned (per row up to V (key image, token) pairs; W*V of them do not fit the LDS).
+ * A group's result does not depend on G or on the other groups of the launch; two launches give the same bytes.
+ * (Timing aid: with SPMM_SBS_PHASES = 1, 2 or 3 in the environment the kernel stops after its first, second or third phase and writes
+ * no output; tools/bench_distinct.py times the phases with it.)
+ * Refused before a launch (rc = 1): G < 0; W outside [1, 1024]; V outside [4, 512]; Lmax outside [2, 256]; without t_ptr a t outside
+ * [0, Lmax - 1); ldl or ldn < V; anc_ld < Lmax; G*W*512 >= 2^31; with G > 0 a null logits, noise, ws, state array (in or out), ids_out or
+ * open_out, a pointer (other than fin_in / fin_out) not 4-byte aligned (ws: 8), an _out array equal to its _in twin.  G == 0 returns 0 without a
+ * launch. */
+int spmm_sbs_step(const float* logits, long ldl, const float* noise, long ldn, int G, int W, int V, int Lmax, int t, const int* t_ptr,
+                  int t_off, const float* phi_in, const float* gum_in, const unsigned char* fin_in, const int* len_in,
+                  const int* tokens_in, const int* anc_in, float* phi_out, float* gum_out, unsigned char* fin_out, int* len_out,
+                  int* tokens_out, int* anc_out, int anc_ld, int* ids_out, int* parent_out, int* open_out, unsigned int* ws,
+                  spmm_stream_t stream);
+
 /* Prefill of the decoder's self-attention cache (csrc/prefill.hip): the keys and values of E whole prefixes, computed by one packed pass,
  * moved into the head-major caches of spmm_decode_attn -- keys and values of a layer in ONE launch.
  * Source: K, V bf16 token-major rows with row stride ld elements, head h at column h*64 -- the K and V column blocks of the fused Q|K|V

@@ -7,6 +7,7 @@ stochastic k-beam search with k = 2, any subset of the 53 properties left unspec
   python pv2smiles.py ... --prefix c1ccccc1                                               (every molecule starts with this SMILES fragment)
   python pv2smiles.py ... --guidance 2 --temperature 0.8 --top_k 40 --top_p 0.95          (the distribution the samples are drawn from)
   python pv2smiles.py ... --syntax                                                        (only well-formed SMILES strings are generated)
+  python pv2smiles.py ... --distinct --n_generate 1000                                    (1000 DIFFERENT token sequences: sampling without replacement)
 
 --guidance w is classifier-free guidance between the requested condition and the same decoder with every property masked,
 log p~ = log p_u + w (log p_c - log p_u): 1 (default) is the conditioned model alone, w > 1 pushes the samples towards the requested
@@ -20,6 +21,14 @@ dot, a non-empty molecule.  Syntax only: element symbols, valence and aromaticit
 generated, and a ring closed on the atom that opened it (C11) passes.  Off by default; with a --prefix that is not the beginning of such a
 string, or cannot be closed in --max_steps tokens, the run stops before anything is decoded.  `well-formed: n / N` (the same automaton
 over the N strings written, without RDKit) is reported with and without the flag.
+
+--distinct replaces the n independent k-beam searches by ONE stochastic beam search (Kool, van Hoof, Welling 2019;
+spmm_amd.decode.sample_distinct): --n_generate (<= 1024) token sequences drawn WITHOUT replacement from the model's distribution, so no
+two of them are equal, in sampling order; the same --seed with a larger --n_generate extends the list.  It composes with --seed, --prefix,
+--temperature, --top_k, --top_p, --syntax and --max_steps; --guidance other than 1 and --stochastic False are refused, --k and --chunk are
+ignored.  Sequences still open after --max_steps positions are dropped and counted, so fewer than --n_generate lines may be written.  Two
+token sequences can spell the same string (WordPiece splits a string in more than one way): the count of distinct strings is printed, and
+nothing is filtered.
 
 What differs from the reference, on purpose: the seed is a flag (the reference draws one at random) and the same seed gives the same
 molecules whatever `--chunk` is; all samples of a chunk are decoded together against a K/V cache (spmm_amd.decode.generate_with_property);
@@ -126,13 +135,29 @@ def report(samples, smiles, prop_input, prop_mask, norm, names):
     print(f"mean of controlled properties' normalized RMSE: {rmse.mean().item():.4f}")
 
 
+DISTINCT_MAX = 1024       # spmm_amd.decode.DISTINCT_MAX: the slots of one stochastic beam search
+
+
+def distinct_args(args):
+    """--distinct against the other flags, before anything is built: SystemExit for what it cannot do, else the lines to print."""
+    if args.n_generate < 1 or args.n_generate > DISTINCT_MAX:
+        raise SystemExit(f"pv2smiles.py --distinct: --n_generate {args.n_generate} outside [1, {DISTINCT_MAX}]: one search draws at most {DISTINCT_MAX} "
+                         "distinct sequences per property vector")
+    if float(args.guidance) != 1.0:
+        raise SystemExit(f"pv2smiles.py --distinct: --guidance {args.guidance:g} is not available with --distinct (guidance 1 only)")
+    if not args.stochastic:
+        raise SystemExit("pv2smiles.py --distinct: --stochastic False asks for the deterministic beam search; --distinct is a sampling method")
+    return [f"distinct: one stochastic beam search of {args.n_generate} slots; --k {args.k} and --chunk {args.chunk} are ignored"]
+
+
 # ------------------------------------------------------------------------------------------------------------------- main
 def main(args):
     device = torch.device(args.device)
     torch.manual_seed(args.seed)
     from spmm_amd import decode
+    distinct_lines = distinct_args(args) if args.distinct else None
     try:
-        warp = decode.check_warp(args.guidance, args.temperature, args.top_k, args.top_p, args.k)       # (before the model is built)
+        warp = decode.check_warp(args.guidance, args.temperature, args.top_k, args.top_p, 1 if args.distinct else args.k)       # (before the model is built)
     except ValueError as e:
         raise SystemExit(f"pv2smiles.py: {e}")
     from spmm_amd.model import SPMM
@@ -188,17 +213,26 @@ def main(args):
         except ValueError as e:
             raise SystemExit(f"pv2smiles.py --syntax: {str(e).removeprefix('syntax: ')}")
         print("syntax: every position is constrained to well-formed SMILES (syntax only: no elements, valence, aromaticity, %nn)")
-    print(f"PV-to-SMILES generation in {'stochastic' if args.stochastic else 'deterministic'} manner with k={args.k}, seed {args.seed}...")
+    if args.distinct:
+        print("\n".join(distinct_lines))
+        print(f"PV-to-SMILES generation of {args.n_generate} distinct token sequences (sampling without replacement), seed {args.seed}...")
+    else:
+        print(f"PV-to-SMILES generation in {'stochastic' if args.stochastic else 'deterministic'} manner with k={args.k}, seed {args.seed}...")
     prefix = prefix_ids(tokenizer, args.prefix) if args.prefix else None
     if warp is not None:
         print(f"sampling: guidance {warp['guidance']:g}, temperature {warp['temperature']:g}, top_k {warp['top_k']}, top_p {warp['top_p']:g}")
     if prefix is not None:
         print(f"prefix: {args.prefix!r} ({len(prefix)} tokens with [CLS]); every molecule starts with it")
     try:
-        samples = decode.generate_with_property(model, pv.to(device), args.n_generate, prop_mask.to(device), k=args.k, stochastic=args.stochastic,
-                                                seed=args.seed, max_steps=args.max_steps, chunk=args.chunk or None, prefix=prefix,
-                                                guidance=args.guidance, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-                                                syntax=syntax)
+        if args.distinct:
+            found = decode.sample_distinct(model, pv.to(device), args.n_generate, prop_mask.to(device), seed=args.seed, max_steps=args.max_steps,
+                                           prefix=prefix, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, syntax=syntax)[0]
+            samples = [ids for _, ids in found]
+        else:
+            samples = decode.generate_with_property(model, pv.to(device), args.n_generate, prop_mask.to(device), k=args.k, stochastic=args.stochastic,
+                                                    seed=args.seed, max_steps=args.max_steps, chunk=args.chunk or None, prefix=prefix,
+                                                    guidance=args.guidance, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+                                                    syntax=syntax)
     except ValueError as e:
         if syntax is None or not str(e).startswith("syntax:"):
             raise
@@ -211,6 +245,10 @@ def main(args):
     if prefix is not None:
         print(f"prefix: {args.prefix} ({len(prefix)} tokens)")
     report(samples, smiles, prop_input, prop_mask, norm, names)
+    if args.distinct:
+        run = decode.last_distinct
+        print(f"distinct: {len({tuple(s) for s in samples})} token sequences, {len(set(smiles))} strings / {args.n_generate} requested")
+        print(f"finished: {run['finished'][0]}, unfinished after {args.max_steps} positions (dropped): {run['unfinished'][0]}, empty slots: {run['empty'][0]}")
     print(f"Generated molecules are saved in '{args.output}'")
     print("=" * 50)
     return smiles
@@ -241,6 +279,8 @@ def parse_args(argv=None):
     p.add_argument("--top_p", default=1.0, type=float, help="nucleus: keep the most probable tokens until their probability reaches p, in (0, 1] (1: all)")
     p.add_argument("--syntax", action="store_true", help="generate well-formed SMILES strings only (syntax: parentheses, ring bonds, bracket atoms, "
                    "bonds; not elements, valence or aromaticity)")
+    p.add_argument("--distinct", action="store_true", help="--n_generate (<= 1024) DIFFERENT token sequences by one stochastic beam search (sampling "
+                   "without replacement) instead of independent searches; ignores --k and --chunk")
     p.add_argument("--synthetic", action="store_true", help="no data files: seeded weights, property vector and vocabulary")
     p.add_argument("--tiny", action="store_true", help="2-layer / 128-d encoders (configs/config_bert_tiny.json)")
     return p.parse_args(argv)

@@ -658,11 +658,15 @@ class GuidedDecoder(CachedDecoder):
     The warp is the kernel where the one-launch beam step runs (k <= 8, V <= 512, FUSED_BEAM_STEP), else warp_logits."""
 
     def __init__(self, model, prop_embeds: torch.Tensor, k: int, Lmax: int, repeat: int = 1, xkv: dict | None = None, memory: dict | None = None, *,
-                 base_embeds: torch.Tensor | None = None, guidance: float = 1.0, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+                 base_embeds: torch.Tensor | None = None, guidance: float = 1.0, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                 min_keep: int | None = None):
+        """min_keep (None: k): the tokens every row keeps whatever the truncation says -- k for the searches that draw k tokens per row, 1
+        for sample_distinct, whose rows contribute any number of candidates."""
         if memory is not None:
             raise ValueError("guidance contrasts a property condition with the all-masked one; a decoder with memory= (reaction prediction) "
                              "has no such baseline")
-        self.warp = check_warp(guidance, temperature, top_k, top_p, k) or dict(NO_WARP)
+        self.min_keep = k if min_keep is None else int(min_keep)
+        self.warp = check_warp(guidance, temperature, top_k, top_p, self.min_keep) or dict(NO_WARP)
         if base_embeds is None and self.warp["guidance"] != 1.0:
             raise ValueError(f"guidance={guidance} needs base_embeds, the encoded all-masked PV")
         Nc = prop_embeds.shape[0]
@@ -686,8 +690,8 @@ class GuidedDecoder(CachedDecoder):
         if self.premask is not None:                                      # both halves alike: masking lc alone would be wrong for w <= 0
             self.premask(lc, lu, by=by)
         if self.fused_warp:
-            return ops.logit_warp(lc, lu, w=w["guidance"], temperature=w["temperature"], top_k=w["top_k"], top_p=w["top_p"], min_keep=self.k)
-        return warp_logits(lc, lu, guidance=w["guidance"], temperature=w["temperature"], top_k=w["top_k"], top_p=w["top_p"], min_keep=self.k)
+            return ops.logit_warp(lc, lu, w=w["guidance"], temperature=w["temperature"], top_k=w["top_k"], top_p=w["top_p"], min_keep=self.min_keep)
+        return warp_logits(lc, lu, guidance=w["guidance"], temperature=w["temperature"], top_k=w["top_k"], top_p=w["top_p"], min_keep=self.min_keep)
 
     def _expand_xkv(self, xkv: dict):
         """The conditioned half as CachedDecoder expands it; the baseline half reads ONE copy, the all-masked row's projection."""
@@ -767,8 +771,9 @@ class GuidedRecompute:
     decoder per condition and warp_logits.  The yard-stick of the cached route."""
 
     def __init__(self, model, prop_embeds: torch.Tensor, k: int, Lmax: int, *, base_embeds: torch.Tensor | None = None, guidance: float = 1.0,
-                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
-        self.warp = check_warp(guidance, temperature, top_k, top_p, k) or dict(NO_WARP)
+                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, min_keep: int | None = None):
+        self.min_keep = k if min_keep is None else int(min_keep)         # (GuidedDecoder's)
+        self.warp = check_warp(guidance, temperature, top_k, top_p, self.min_keep) or dict(NO_WARP)
         if base_embeds is None and self.warp["guidance"] != 1.0:
             raise ValueError(f"guidance={guidance} needs base_embeds, the encoded all-masked PV")
         self.k, self.device = k, prop_embeds.device
@@ -782,7 +787,7 @@ class GuidedRecompute:
         if self.premask is not None:
             self.premask(lc, lu, by=by)
         return warp_logits(lc.float(), None if lu is None else lu.float(), guidance=w["guidance"], temperature=w["temperature"], top_k=w["top_k"],
-                           top_p=w["top_p"], min_keep=self.k)
+                           top_p=w["top_p"], min_keep=self.min_keep)
 
     def step(self, ids: torch.Tensor, t: int) -> torch.Tensor:
         return self._warped(self.cond.step(ids, t), None if self.base is None else self.base.step(ids, t))
@@ -1099,6 +1104,241 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
                          **{f: last_run.get(f, v) for f, v in dict(NO_WARP, baseline_rows=0).items()}, syntax=syntax is not None,
                          dropped_masked=dropped)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Distinct samples: stochastic beam search (Kool, van Hoof, Welling 2019) -- sequences sampled WITHOUT replacement
+# ------------------------------------------------------------------------------------------------------------------
+DISTINCT_SALT = 0x53425331      # call-site salt of the distinct search's noise ("SBS1")
+DISTINCT_MAX = 1024             # samples per property vector (spmm_sbs_step's W)
+SBS_ALLOWED_ABOVE = -1e29       # a logit at or below this (-inf, the syntax mask's -1e30) is no candidate (spmm_sbs_step)
+last_distinct: dict = {}        # what the last sample_distinct did: groups, W, n_distinct, positions, finished, unfinished, empty (per group, over
+#                                 the first n_distinct slots), dropped_masked, fused, prefix_tokens, temperature, top_k, top_p, syntax, min_gap (the
+#                                 tensor-op form: the smallest gap between unequal neighbouring keys a decision hung on; None on the kernel)
+
+
+class DistinctBook:
+    """The state of stochastic beam search for G property vectors x W slots, double-buffered: per slot the log-probability `phi` of its
+    hypothesis, its perturbed key `gum` (-inf: the slot is empty), `fin`, `len`, the token history and the K/V ancestry row.  A step reads
+    the current buffers and writes the others, then they swap: `step_fused` is the one-launch form (ops.sbs_step; fp32 state), `update`
+    the same step as tensor ops in float64 (any device; whole-prefix decoders, shapes the kernel refuses, FUSED_BEAM_STEP = False).
+    The search starts with slot 0 at phi = 0, gum = 0 and every other slot empty: the first position is a step like any other.
+    `mol` is None and `tokens` / `t` read as BeamBook's: a SyntaxMask takes this book as it takes that one."""
+    FIELDS = ("phi", "gum", "fin", "len", "tokens", "anc")
+
+    def __init__(self, G: int, W: int, max_steps: int, device, fused: bool = False, prefix: torch.Tensor | None = None, anc: torch.Tensor | None = None):
+        """prefix (int [G, P], P >= 1, prefix[:, 0] = [CLS]): every hypothesis of group g starts from prefix[g].  anc: the decoder's ancestry
+        table after a prefill (None: every row reads its own cache row everywhere)."""
+        P = 1 if prefix is None else int(prefix.shape[1])
+        self.G, self.W, self.P, self.Lmax, self.fused = G, W, P, P + max_steps + 2, bool(fused)
+        ft, it = (torch.float32, torch.int32) if fused else (torch.float64, torch.long)
+        L = self.Lmax
+
+        def state():
+            return dict(phi=torch.full((G, W), -float("inf"), dtype=ft, device=device), gum=torch.full((G, W), -float("inf"), dtype=ft, device=device),
+                        fin=torch.zeros(G, W, dtype=torch.uint8, device=device), len=torch.zeros(G, W, dtype=it, device=device),
+                        tokens=torch.zeros(G, W, L, dtype=it, device=device),
+                        anc=torch.arange(G * W, dtype=torch.int32, device=device)[:, None].repeat(1, L).contiguous())
+
+        self.cur, self.nxt = state(), state()
+        c = self.cur
+        c["phi"][:, 0] = 0.0
+        c["gum"][:, 0] = 0.0
+        if prefix is None:
+            c["tokens"][:, :, 0] = CLS_ID
+        else:
+            c["tokens"][:, :, :P] = prefix.to(device).to(it)[:, None, :]
+        c["len"][:] = P
+        if anc is not None:
+            c["anc"].copy_(anc.reshape(G * W, L))
+        self.t = P                                        # tokens held by every live slot
+        self.open = torch.full((G,), W, dtype=torch.int32, device=device)
+        self.ws = None                                    # the kernel's scratch (ops.sbs_step sizes it)
+        self.mol = None
+        self.parent = None                                # update: the parents of the last step, int64 [G, W]
+        self.min_gap = float("inf")                       # update: the smallest gap between two unequal neighbours among the W + 1 best keys so far
+
+    tokens = property(lambda self: self.cur["tokens"].view(self.G * self.W, self.Lmax))
+    anc = property(lambda self: self.cur["anc"])
+
+    def step_fused(self, logits: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+        """One position as one launch: logits, noise fp32 [G*W, V] -> the tokens to feed next, int32 [G*W] (0 for finished and empty slots)."""
+        ids = ops.sbs_step(logits, noise, self, t=self.t)
+        self.cur, self.nxt = self.nxt, self.cur
+        self.t += 1
+        return ids
+
+    def update(self, logits: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+        """`step_fused` as tensor ops in float64 (the rules of spmm_sbs_step, include/spmm_hip.h) -> the tokens to feed next, int64 [G*W]."""
+        G, W, L, t = self.G, self.W, self.Lmax, self.t
+        c, n = self.cur, self.nxt
+        V = logits.shape[-1]
+        NEG = -float("inf")
+        l, nz = logits.double().reshape(G, W, V), noise.double().reshape(G, W, -1)[:, :, :V].to(logits.device)
+        T, phi, fin = c["gum"].double(), c["phi"].double(), c["fin"].bool()
+        used = T > NEG
+        live, done = used & ~fin, used & fin
+        ok = (l > SBS_ALLOWED_ABOVE) & live[:, :, None]
+        neg = torch.full_like(l, NEG)
+        m = torch.where(ok, l, neg).max(-1, keepdim=True).values
+        m0 = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+        lse = m0 + torch.log(torch.where(ok, torch.exp(l - m0), torch.zeros_like(l)).sum(-1, keepdim=True))
+        cphi = phi[:, :, None] + (l - lse)
+        g = torch.where(ok, cphi + nz, neg)
+        Z = g.max(-1, keepdim=True).values
+        v = T[:, :, None] - g + torch.log1p(-torch.exp(g - Z))
+        key = T[:, :, None] - v.clamp_min(0.0) - torch.log1p(torch.exp(-v.abs()))
+        key = torch.where(ok & ~torch.isnan(key), key, neg)
+        key[:, :, SEP_ID] = torch.where(done, T, key[:, :, SEP_ID])                 # a finished slot's one candidate: itself
+        cphi[:, :, SEP_ID] = torch.where(done, phi, cphi[:, :, SEP_ID])
+        skey, flat = torch.sort(key.reshape(G, W * V), dim=1, descending=True, stable=True)      # (stable: equal keys keep their flat-index order)
+        top = skey[:, :W + 1]                            # the cut and the slot order hang on the gaps between these
+        gaps = (top[:, :-1] - top[:, 1:])[(top[:, 1:] > NEG) & (top[:, :-1] > top[:, 1:])]
+        if gaps.numel():
+            self.min_gap = min(self.min_gap, float(gaps.min()))
+        skey, flat = skey[:, :W], flat[:, :W]
+        have = skey > NEG
+        parent = torch.where(have, flat // V, torch.arange(W, device=flat.device)[None, :].expand(G, W))
+        tok = torch.where(have, flat % V, torch.zeros_like(flat))
+        pfin = fin.gather(1, parent) & have
+        nfin = have & (pfin | (tok == SEP_ID))
+        n["gum"] = torch.where(have, skey, torch.full_like(skey, NEG)).to(c["gum"].dtype)
+        n["phi"] = torch.where(have, cphi.reshape(G, W * V).gather(1, flat), torch.full_like(skey, NEG)).to(c["phi"].dtype)
+        n["fin"] = nfin.to(torch.uint8)
+        n["len"] = torch.where(have, torch.where(pfin, c["len"].gather(1, parent), torch.full_like(c["len"], t + 1)), torch.zeros_like(c["len"]))
+        tokens = c["tokens"].gather(1, parent[:, :, None].expand(G, W, L))
+        tokens[:, :, t] = torch.where(pfin, tokens[:, :, t], tok.to(tokens.dtype))
+        n["tokens"] = torch.where(have[:, :, None], tokens, torch.zeros_like(tokens))
+        rows = torch.arange(G * W, device=flat.device).view(G, W)
+        prow = (rows[:, :1] + parent).reshape(-1)
+        own = rows.reshape(-1, 1).to(torch.int32).expand(G * W, L)
+        inherit = (torch.arange(L, device=flat.device)[None, :] < t) & have.reshape(-1, 1)
+        n["anc"] = torch.where(inherit, c["anc"][prow], own).contiguous()
+        self.open = (have & ~nfin).sum(1).to(torch.int32)
+        self.parent = parent
+        self.cur, self.nxt = n, c
+        self.t = t + 1
+        return torch.where(have & ~nfin, tok, torch.zeros_like(tok)).reshape(-1)
+
+    def results(self, n_first: int | None = None):
+        """-> (per group the finished hypotheses among the first n_first slots, in slot order, as (logp, token ids); unfinished [G]; empty [G])."""
+        n_first = self.W if n_first is None else n_first
+        c = self.cur
+        gum, phi, fin = c["gum"][:, :n_first].cpu(), c["phi"][:, :n_first].cpu(), c["fin"][:, :n_first].cpu().bool()
+        ln, tk = c["len"][:, :n_first].cpu(), c["tokens"][:, :n_first].cpu()
+        used = gum > -float("inf")
+        out = [[(float(phi[g, s]), tk[g, s, : int(ln[g, s])].tolist()) for s in range(n_first) if used[g, s] and fin[g, s]] for g in range(self.G)]
+        return out, (used & ~fin).sum(1).tolist(), (~used).sum(1).tolist()
+
+
+@torch.no_grad()
+def sample_distinct(model, props: torch.Tensor, n_distinct: int, prop_mask: torch.Tensor | None = None, seed: int = 0, max_steps: int = 100,
+                    cached: bool | None = None, sync_every: int = 4, prefix=None, prefill: bool = True, temperature: float = 1.0, top_k: int = 0,
+                    top_p: float = 1.0, syntax=None, guidance: float = 1.0, pv_base: int = 0) -> List[List[Tuple[float, List[int]]]]:
+    """n_distinct DIFFERENT token sequences per property vector: stochastic beam search (Kool, van Hoof, Welling 2019), an exact sample
+    without replacement from the model's sequence distribution.  props [53] or [G, 53]; result[g]: the finished hypotheses among the first
+    n_distinct slots as (log-probability, token ids [CLS] .. [SEP]), in slot order -- sampling order, not probability order.  Hypotheses
+    still open after max_steps positions are dropped and counted (last_distinct).
+    The search runs W = n_distinct rounded up to a multiple of 8 slots and returns the first n_distinct: the noise of (seed, group,
+    position, slot, token) does not depend on W (ops.gumbel_noise, k = 8, molecule (pv_base + g) * 128 + slot // 8), a slot's key never
+    exceeds its parent's, and so the first n slots of a wider search ARE the n-slot search: one seed gives one ordered list of distinct
+    sequences, and asking for more extends it.
+    One launch per position for the bookkeeping where spmm_sbs_step takes the shape (cached decoder, vocabulary <= 512, <= 256 positions,
+    FUSED_BEAM_STEP), the float64 tensor-op form elsewhere.  The decoder is CachedDecoder(k = 8, repeat = W / 8) reading the book's current
+    ancestry table (cached=False: the whole-prefix decoder); a finished slot's row keeps being stepped with token 0.  The search stays eager.
+    prefix, prefill, syntax, temperature, top_k, top_p: beam_search_batched's, with min_keep = 1 (a row contributes any number of
+    candidates); the log-probabilities returned are those of the warped distribution renormalised over the kept and allowed tokens.  A
+    masked token is no candidate here, so no hypothesis goes through one.  guidance != 1 is not built: ValueError."""
+    if float(guidance) != 1.0:
+        raise ValueError(f"guidance={guidance}: classifier-free guidance is out of scope for sample_distinct (guidance = 1 only)")
+    if isinstance(n_distinct, bool) or int(n_distinct) != n_distinct or not 1 <= int(n_distinct) <= DISTINCT_MAX:
+        raise ValueError(f"n_distinct={n_distinct!r} outside [1, {DISTINCT_MAX}]: the search holds at most {DISTINCT_MAX} slots per property vector")
+    n_distinct = int(n_distinct)
+    warp = check_warp(1.0, temperature, top_k, top_p, 1)
+    if cached is None:
+        cached = hasattr(model, "engine")
+    props = props.reshape(-1, props.shape[-1])
+    G = props.shape[0]
+    prefix = check_prefix(prefix, G, _vocab_size(model), max_steps)
+    table = syntax_table(model, syntax, prefix, max_steps)
+    P = 1 if prefix is None else prefix.shape[1]
+    Lmax = P + max_steps + 2
+    if Lmax > DECODE_MAXL:
+        raise ValueError(f"P + max_steps + 2 = {P} + {max_steps} + 2 exceeds the {DECODE_MAXL} positions the decode kernels hold")
+    W = (n_distinct + 7) // 8 * 8
+    R = W // 8
+    prop_embeds = encode_properties(model, props, prop_mask)
+    dev = prop_embeds.device
+    if cached:
+        model.engine.train_mode = False
+        dec = (CachedDecoder(model, prop_embeds, 8, Lmax, repeat=R) if warp is None else
+               GuidedDecoder(model, prop_embeds, 8, Lmax, repeat=R, min_keep=1, **warp))
+    else:
+        dec = (RecomputeDecoder(model, prop_embeds, W, Lmax) if warp is None else GuidedRecompute(model, prop_embeds, W, Lmax, min_keep=1, **warp))
+    V = _vocab_size(model)
+    fused = bool(cached and FUSED_BEAM_STEP and V is not None and 4 <= V <= 512)
+    mask = None
+    pom = torch.arange(G * R) // R if cached else torch.arange(G)        # the (PV, prefix) pair of every decoder molecule: its group
+    if prefix is not None:
+        prefix = prefix.expand(G, P)
+    if table is not None:
+        mask = SyntaxMask(table, 8 if cached else W, P, max_steps, dev, kernel=fused)
+        mask.start(prefix, pom, len(pom))
+    if hasattr(dec, "premask"):
+        dec.premask, own_mask = mask, None
+    else:
+        own_mask = mask
+    if prefix is None:
+        logits = dec.step(torch.full((G * W,), CLS_ID, dtype=torch.long, device=dev), 0)
+        if own_mask is not None:
+            own_mask(logits, by="row")
+    else:
+        logits = dec.prefill(prefix, pom, by_steps=not prefill)              # [G, V]: one pair per group
+        if own_mask is not None:
+            own_mask(logits, by="pair")
+        logits = logits.repeat_interleave(W, dim=0)
+    V = logits.shape[-1]
+    book = DistinctBook(G, W, max_steps, dev, fused=fused, prefix=prefix, anc=dec.anc if cached else None)
+    mols = ((pv_base + torch.arange(G))[:, None] * 128 + torch.arange(R)[None, :]).reshape(-1)
+    if fused:
+        seed_dev = torch.tensor([(int(seed) & _M64) - ((int(seed) & (1 << 63)) << 1)], dtype=torch.int64, device=dev)
+        mol_dev = mols.to(torch.int32).to(dev)
+        nbuf = torch.empty(G * W, V, dtype=torch.float32, device=dev)
+
+    def noise(t):
+        """Keyed by the absolute position of the last token held, as the seeded beam search keys its draws."""
+        if fused:
+            return ops.gumbel_noise(seed_dev, G * R, 8, V, Lmax, salt=DISTINCT_SALT, t=t, mol=mol_dev, out=nbuf)
+        return gumbel_noise_host(seed, DISTINCT_SALT, mols.tolist(), t, 8, V, Lmax)
+
+    def advance(logits):
+        ids = book.step_fused(logits.float(), noise(book.t - 1)) if fused else book.update(logits, noise(book.t - 1))
+        if cached:
+            dec.anc = book.anc                           # the decoder reads the book's current table; cache rows never move
+        else:
+            dec.reorder(book.parent, book.t - 1)
+        return ids
+
+    last_distinct.clear()
+    ids = advance(logits)
+    if mask is not None:
+        mask.book = book
+    positions = 0
+    for s in range(max_steps):
+        if s % sync_every == 0 and int(book.open.sum().item()) == 0:         # the one host read of the loop
+            break
+        logits = dec.step(ids, P + s)
+        if own_mask is not None:
+            own_mask(logits)
+        ids = advance(logits)
+        positions = s + 1
+    res, unfinished, empty = book.results(n_distinct)
+    kept = [[h for h in hyps if h[0] > SYNTAX_DROP_BELOW] for hyps in res]
+    last_distinct.update(groups=G, W=W, n_distinct=n_distinct, positions=positions, finished=[len(h) for h in kept], unfinished=unfinished, empty=empty,
+                         dropped_masked=sum(len(a) - len(b) for a, b in zip(res, kept)), fused=fused, prefix_tokens=P,
+                         min_gap=None if fused else book.min_gap,
+                         **{f: (warp or NO_WARP)[f] for f in ("temperature", "top_k", "top_p")}, syntax=mask is not None)
+    return kept
 
 
 # ------------------------------------------------------------------------------------------------------------------

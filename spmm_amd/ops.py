@@ -651,6 +651,36 @@ def gumbel_noise(seed, N, k, V, Lmax, *, salt=0, t=0, t_ptr=None, t_off=0, mol=N
     return out
 
 
+SBS_MAXW = 1024         # spmm_sbs_step: slots per property vector
+
+
+def sbs_step(logits, noise, book, *, t=0, t_ptr=None, t_off=0, ids_out=None, parent_out=None):
+    """One position of stochastic beam search on a decode.DistinctBook with fp32 / int32 state (csrc/sbs.hip, spmm_sbs_step): reads the
+    book's current buffers, writes its other ones -- the caller swaps them (DistinctBook.step_fused) -- and returns the tokens to feed
+    next, int32 [G*W].  logits, noise: fp32 [G*W, V] (noise may be wider)."""
+    cur, nxt = book.cur, book.nxt
+    G, W, L = cur["tokens"].shape
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[0] == G * W and logits.stride(1) == 1
+    V = logits.shape[1]
+    assert noise.dtype == torch.float32 and noise.dim() == 2 and noise.stride(1) == 1 and noise.device == logits.device
+    assert noise.shape[0] == G * W and noise.shape[1] >= V, (noise.shape, logits.shape)
+    for s in (cur, nxt):
+        assert s["phi"].dtype == torch.float32 and s["gum"].dtype == torch.float32 and s["fin"].dtype == torch.uint8
+        assert s["len"].dtype == torch.int32 and s["tokens"].dtype == torch.int32 and s["anc"].dtype == torch.int32
+        assert all(s[f].is_contiguous() for f in ("phi", "gum", "fin", "len", "tokens")) and s["anc"].stride(1) == 1
+        assert s["anc"].shape[0] == G * W and s["anc"].shape[1] >= L
+    assert cur["anc"].stride(0) == nxt["anc"].stride(0)
+    if ids_out is None:
+        ids_out = torch.empty(G * W, dtype=torch.int32, device=logits.device)
+    if book.ws is None or book.ws.numel() < 2 * G * W * V:
+        book.ws = torch.empty(2 * G * W * V, dtype=torch.int32, device=logits.device)
+    _call("spmm_sbs_step", _p(logits), logits.stride(0), _p(noise), noise.stride(0), G, W, V, L, int(t), _p(t_ptr), int(t_off),
+          _p(cur["phi"]), _p(cur["gum"]), _p(cur["fin"]), _p(cur["len"]), _p(cur["tokens"]), _p(cur["anc"]),
+          _p(nxt["phi"]), _p(nxt["gum"]), _p(nxt["fin"]), _p(nxt["len"]), _p(nxt["tokens"]), _p(nxt["anc"]), cur["anc"].stride(0),
+          _p(ids_out), _p(parent_out), _p(book.open), _p(book.ws), _st())
+    return ids_out
+
+
 def logit_warp(lc, lu=None, *, w=1.0, temperature=1.0, top_k=0, top_p=1.0, min_keep=1, out=None):
     """Guidance, temperature, top-k and nucleus truncation of next-token logits in one launch (csrc/warp.hip, spmm_logit_warp; the
     tensor-op twin is decode.warp_logits): lc fp32 [R, V] conditioned logits, lu (optional, same shape and row stride) the all-masked
