@@ -29,7 +29,7 @@ sys.path.insert(0, ROOT)
 from pv2smiles import read_normalize, synthetic_vocab                       # noqa: E402
 from rxn_predict import MAX_SOURCE, synthetic_reactions                     # noqa: E402
 from score import read_pairs                                                # noqa: E402
-from smiles2pv import encode, length_sorted_batches, pad_batch, read_smiles, synthetic_smiles      # noqa: E402
+from smiles2pv import add_tokenizer_flags, encode, length_sorted_batches, library_of, pad_batch, read_smiles, synthetic_smiles      # noqa: E402,F401
 
 N_PROPS = 53
 MAX_LENGTH = 100
@@ -220,11 +220,13 @@ def main(args):
     kw = dict(layers=args.layers, heads=args.heads)
     if args.rxn:
         sources, smiles = synthetic_reactions(itos, args.synthetic, args.seed) if args.synthetic else read_pairs(args.input_file)
-        src_rows, rows_t = encode(tokenizer, sources, MAX_SOURCE), encode(tokenizer, smiles, MAX_LENGTH)
+        src_lib = library_of(tokenizer, sources, MAX_SOURCE, model, args.host_tokenizer)
+        lib_t = library_of(tokenizer, smiles, MAX_LENGTH, model, args.host_tokenizer)
+        src_rows, rows_t = src_lib.host_rows(), lib_t.host_rows()                      # (the token labels of the CSV)
 
         def run_batch(idx):
-            sid, smask = pad_batch([src_rows[i] for i in idx], pad)
-            ids, mask = pad_batch([rows_t[i] for i in idx], pad)
+            sid, smask, _ = src_lib.take(idx)
+            ids, mask, _ = lib_t.take(idx)
             maps = AT.reaction_attention_maps(model, sid, smask, ids, mask, **kw)
             return [{(l, d): maps.get(p, l, d).cpu().numpy() for l in maps.layers for d in maps.directions} for p in range(len(idx))]
         qlab = [token_labels(itos, r) for r in rows_t]
@@ -232,7 +234,8 @@ def main(args):
     else:
         names = read_property_names(args.property_names)
         smiles = synthetic_smiles(itos, args.synthetic, args.seed) if args.synthetic else read_smiles(args.input_file)
-        rows_t = encode(tokenizer, smiles, MAX_LENGTH)
+        lib_t = library_of(tokenizer, smiles, MAX_LENGTH, model, args.host_tokenizer)
+        rows_t = lib_t.host_rows()                                                     # (the token labels of the CSV)
         prop_mask = mask_from_names(args.mask_properties, names) if args.mask_properties else None
         pv_all = None
         if args.pv_csv:
@@ -245,8 +248,8 @@ def main(args):
 
         def run_batch(idx):
             from spmm_amd.decode import predict_properties
-            ids, mask = pad_batch([rows_t[i] for i in idx], pad)
-            pv = pv_all[torch.from_numpy(idx)] if pv_all is not None else predict_properties(model, ids, mask, N_PROPS).float()
+            ids, mask, n_tokens = lib_t.take(idx)
+            pv = pv_all[torch.from_numpy(idx)] if pv_all is not None else predict_properties(model, ids, mask, N_PROPS, n_tokens=n_tokens).float()
             maps = AT.cross_attention_maps(model, pv, prop_mask, ids, mask, direction=args.direction, **kw)
             return [{(l, d): maps.get(p, l, d).cpu().numpy() for l in maps.layers for d in maps.directions} for p in range(len(idx))]
         plab = property_labels(names)
@@ -300,6 +303,7 @@ def parse_args(argv=None):
     p.add_argument("--seed", default=0, type=int, help="seed of --synthetic's weights and input")
     p.add_argument("--synthetic", default=0, type=int, metavar="N", help="no data files: seeded weights, N made-up molecules (or reactions)")
     p.add_argument("--tiny", action="store_true", help="2-layer / 128-d encoders (configs/config_bert_tiny.json)")
+    add_tokenizer_flags(p)
     return p.parse_args(argv)
 
 

@@ -308,6 +308,29 @@ int spmm_smiles_mask(float* logits, float* logits2, long ld, int R, int V, const
                      const int* mol, int Lmax, int t, const int* t_ptr, int t_off, int t_last, const int* table, int* state_out,
                      spmm_stream_t stream);
 
+/* Device WordPiece (csrc/tokenize.hip; spmm_amd/tokenizer.py::SmilesWordPiece is normative, spmm_amd/wordpiece_device.py builds the table and
+ * holds the host form of the walk): the token rows of N strings in ONE launch, as tokenizer.encode_smiles + pad_rows make them.
+ * blob, offsets: string i is the bytes blob[offsets[i] : offsets[i+1] - gap); offsets int64 [N + 1], non-decreasing by at least gap and inside
+ * the blob (the caller's contract: the kernel reads exactly those bytes); gap = 1 takes "\n".join(strings) as it is.
+ * head [head_len]: the text every word starts with ("[CLS]"); the word of string s is s if s starts with the head, else head + s.
+ * table [table_words]: WordPieceTable.words -- a trie as an open-addressed hash of (node, byte) -> child plus a terminal id per node; layout
+ * in csrc/tokenize.hip.  A table whose header does not describe itself leaves every string to the host (status 2).
+ * Per string, greedy longest-match-first over the word's character positions (position 0: the vocabulary entries as written; later
+ * positions: the '##' entries by their content), followed to the END of the word before anything is cut:
+ *     status 2, lens 0, the row all pad_id   a byte outside 0x21..0x7E anywhere in the string (whitespace splits words, UTF-8 characters
+ *                                            are not bytes): the host tokenises these
+ *     status 1, lens 2, [unk_id, sep_id]     the word is longer than max_chars bytes, or some position the chain reaches matches nothing
+ *                                            (also beyond the max_pieces-th piece)
+ *     status 0, lens c + 1                   the ids of the first c = min(pieces, max_pieces) pieces, then sep_id
+ * ids int32 [N, ld]: every entry of a row is written, pad_id behind its lens[i] entries; lens, status int32 [N].  Nothing needs zeroing.
+ * Integer state only; a row's result does not depend on the rest of the launch.
+ * Refused before a launch (rc = 1): N < 0; gap outside {0, 1}; head_len outside [0, 16]; max_chars outside [1, 256]; max_pieces < 1;
+ * ld < max_pieces + 1; table_words outside [8, 8192]; with N > 0 a null blob, offsets, table, ids, lens or status, a null head with
+ * head_len > 0, a table / ids / lens / status not 4-byte aligned, offsets not 8-byte aligned.  N == 0 returns 0 without a launch. */
+int spmm_wordpiece(const unsigned char* blob, const long* offsets, int N, int gap, const unsigned char* head, int head_len,
+                   const int* table, int table_words, int max_chars, int max_pieces, int unk_id, int sep_id, int pad_id,
+                   int* ids, long ld, int* lens, int* status, spmm_stream_t stream);
+
 /* One position of stochastic beam search (Kool, van Hoof, Welling 2019; csrc/sbs.hip): sequences sampled WITHOUT replacement, for G
  * property vectors ("groups") of W slots each, in ONE launch (one workgroup per group; selection and gather share the launch because
  * every state array has an _out twin, so no input is overwritten before it is read).

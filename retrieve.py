@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from pv2smiles import read_condition, read_normalize, synthetic_vocab      # noqa: E402  (the query is read exactly as pv2smiles.py reads it)
-from smiles2pv import read_smiles, synthetic_smiles                        # noqa: E402  (the library as smiles2pv.py reads its input)
+from smiles2pv import add_tokenizer_flags, read_smiles, synthetic_smiles   # noqa: E402  (the library as smiles2pv.py reads its input)
 
 N_PROPS = 53
 
@@ -111,7 +111,9 @@ def main(args):
     model.eval()
     if library is not None:
         print(f"Encoding {len(library)} molecules...")
-        index = R.MoleculeIndex.build(model, tokenizer, library, batch_size=args.batch_size)
+        from spmm_amd.wordpiece_device import device_tokenizer_for
+        index = R.MoleculeIndex.build(model, tokenizer, library, batch_size=args.batch_size,
+                                      tokenizer_device=device_tokenizer_for(tokenizer, device, args.host_tokenizer))
     else:
         index = R.MoleculeIndex.load(args.index, device=device)
         print(f"Loaded {len(index)} molecules from '{args.index}'")
@@ -161,6 +163,7 @@ def parse_args(argv=None):
     p.add_argument("--seed", default=0, type=int, help="seed of --synthetic's weights, library and query")
     p.add_argument("--synthetic", default=0, type=int, metavar="N", help="no data files: seeded weights, N made-up molecules, a made-up query")
     p.add_argument("--tiny", action="store_true", help="2-layer / 128-d encoders (configs/config_bert_tiny.json)")
+    add_tokenizer_flags(p)
     return p.parse_args(argv)
 
 

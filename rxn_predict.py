@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from pv2smiles import synthetic_vocab                                # noqa: E402
-from smiles2pv import encode, length_sorted_batches, pad_batch      # noqa: E402  ('[CLS]' prefix, the tokenizer's own first token dropped)
+from smiles2pv import add_tokenizer_flags, encode, length_sorted_batches, library_of, pad_batch      # noqa: E402,F401  ('[CLS]' prefix, the tokenizer's own first token dropped)
 
 MAX_SOURCE = 150          # d_rxn_prediction.py:63,92 (tokenizer(text, padding='longest', max_length=150))
 MAX_STEPS = 100           # positions of evaluate / evaluate_beam (:67, :100)
@@ -48,15 +48,16 @@ def read_reactions(path: str):
     return src, tgt
 
 
-def predict_all(model, tokenizer, sources, n_beam: int, batch_size: int, max_steps: int = MAX_STEPS, predict=None, greedy=None):
-    """Candidate id lists of every reaction in INPUT order: result[i] = up to n_beam id lists, best first (one for n_beam == 1)."""
+def predict_all(model, tokenizer, sources, n_beam: int, batch_size: int, max_steps: int = MAX_STEPS, predict=None, greedy=None,
+                host_tokenizer=False):
+    """Candidate id lists of every reaction in INPUT order: result[i] = up to n_beam id lists, best first (one for n_beam == 1).
+    host_tokenizer: --host_tokenizer (the sources go through the Python tokenizer also where the GPU could tokenise them in one launch)."""
     if predict is None or greedy is None:
         from spmm_amd import decode
         predict, greedy = predict or decode.predict_products, greedy or decode.greedy_products
-    rows = encode(tokenizer, sources, MAX_SOURCE)
-    out = [None] * len(rows)
-    for idx in length_sorted_batches([len(r) for r in rows], batch_size):
-        ids, mask = pad_batch([rows[i] for i in idx], tokenizer.pad_token_id)
+    lib = library_of(tokenizer, sources, MAX_SOURCE, model, host_tokenizer)
+    out = [None] * len(lib)
+    for idx, ids, mask, _ in lib.batches(batch_size):
         if n_beam == 1:
             res = [[seq] for seq in greedy(model, ids, mask, max_steps=max_steps)]
         else:
@@ -149,7 +150,7 @@ def main(args):
     model.eval()
     print("=" * 50)
     print(f"{args.mode} reaction prediction, {'greedy' if args.n_beam == 1 else f'{args.n_beam} beams'}, {len(sources)} reactions...")
-    ids = predict_all(model, tokenizer, sources, args.n_beam, args.batch_size, args.max_steps)
+    ids = predict_all(model, tokenizer, sources, args.n_beam, args.batch_size, args.max_steps, host_tokenizer=args.host_tokenizer)
     candidates = [[tokenizer.decode(seq) for seq in cands] for cands in ids]
     write_csv(args.output, sources, candidates, args.n_beam)
     print(f"Candidates are saved in '{args.output}'")
@@ -177,6 +178,7 @@ def parse_args(argv=None):
     p.add_argument("--seed", default=0, type=int, help="seed of --synthetic's weights and reactions")
     p.add_argument("--synthetic", action="store_true", help="no data files: seeded weights, reactions and vocabulary")
     p.add_argument("--tiny", action="store_true", help="2-layer / 128-d decoder (configs/config_bert_tiny.json)")
+    add_tokenizer_flags(p)
     return p.parse_args(argv)
 
 

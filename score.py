@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 
 from pv2smiles import read_condition, read_normalize, synthetic_vocab      # noqa: E402  (the query is read exactly as pv2smiles.py reads it)
 from rxn_predict import MAX_SOURCE, synthetic_reactions                     # noqa: E402
-from smiles2pv import encode, length_sorted_batches, pad_batch, read_smiles, synthetic_smiles      # noqa: E402
+from smiles2pv import TokenLibrary, add_tokenizer_flags, encode, length_sorted_batches, library_of, pad_batch, read_smiles, synthetic_smiles      # noqa: E402,F401
 
 N_PROPS = 53
 MAX_LENGTH = 100          # tokens per scored molecule, as the reference's inference scripts truncate
@@ -66,11 +66,11 @@ def write_csv(path: str, rows):
 
 
 def score_all(token_rows, batch_size: int, score_batch, pad_id: int = 0):
-    """(logp, tokens) of every sequence in INPUT order: the sequences go to `score_batch(index array, ids, mask)` in batches sorted by
-    token length; it returns the batch's (logp, n_tokens)."""
-    logp, tokens = [0.0] * len(token_rows), [0] * len(token_rows)
-    for idx in length_sorted_batches([len(r) for r in token_rows], batch_size):
-        ids, mask = pad_batch([token_rows[i] for i in idx], pad_id)
+    """(logp, tokens) of every sequence in INPUT order: the sequences -- token rows, or a TokenLibrary that holds them on the host or the
+    device -- go to `score_batch(index array, ids, mask)` in batches sorted by token length; it returns the batch's (logp, n_tokens)."""
+    lib = token_rows if isinstance(token_rows, TokenLibrary) else TokenLibrary.from_host(token_rows, pad_id)
+    logp, tokens = [0.0] * len(lib), [0] * len(lib)
+    for idx, ids, mask, _ in lib.batches(batch_size):
         lp, n = score_batch(idx, ids, mask)
         for i, a, b in zip(idx.tolist(), lp.tolist(), n.tolist()):
             logp[i], tokens[i] = float(a), int(b)
@@ -130,10 +130,10 @@ def main(args):
     pad = tokenizer.pad_token_id
     if args.rxn:
         sources, smiles = synthetic_reactions(tokenizer.itos, args.synthetic, args.seed) if args.synthetic else read_pairs(args.library)
-        src_rows = encode(tokenizer, sources, MAX_SOURCE)
+        src_lib = library_of(tokenizer, sources, MAX_SOURCE, model, args.host_tokenizer)
 
         def score_batch(idx, ids, mask):
-            sid, smask = pad_batch([src_rows[i] for i in idx], pad)
+            sid, smask, _ = src_lib.take(idx)
             r = S.score_products(model, sid, smask, ids, mask)
             return r.logp.cpu(), r.n_tokens.cpu()
     else:
@@ -156,7 +156,7 @@ def main(args):
             return r.logp.cpu(), r.n_tokens.cpu()
     print("=" * 50)
     print(f"Scoring {len(smiles)} {'candidates against their sources' if args.rxn else 'molecules under the query'}...")
-    logp, tokens = score_all(encode(tokenizer, smiles, MAX_LENGTH), args.batch_size, score_batch, pad)
+    logp, tokens = score_all(library_of(tokenizer, smiles, MAX_LENGTH, model, args.host_tokenizer), args.batch_size, score_batch, pad)
     rows = score_rows(smiles, logp, tokens)
     write_csv(args.output, rows)
     for r in rows[:10]:
@@ -186,6 +186,7 @@ def parse_args(argv=None):
     p.add_argument("--seed", default=0, type=int, help="seed of --synthetic's weights and input")
     p.add_argument("--synthetic", default=0, type=int, metavar="N", help="no data files: seeded weights, N made-up molecules (or reactions), a made-up query")
     p.add_argument("--tiny", action="store_true", help="2-layer / 128-d encoders (configs/config_bert_tiny.json)")
+    add_tokenizer_flags(p)
     return p.parse_args(argv)
 
 

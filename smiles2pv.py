@@ -25,6 +25,7 @@ sys.path.insert(0, ROOT)
 from pv2smiles import read_normalize, synthetic_vocab      # noqa: E402  (the mean / std file is read exactly as pv2smiles.py reads it)
 # the package's batching helpers, under the names the drivers import
 from spmm_amd.tokenizer import MAX_LENGTH, encode_smiles as encode, length_sorted_batches, pad_rows as pad_batch, with_cls      # noqa: E402,F401
+from spmm_amd.wordpiece_device import TokenLibrary, add_tokenizer_flags, library_of      # noqa: E402,F401  (a file's molecules: host or device rows)
 
 N_PROPS = 53
 
@@ -36,15 +37,16 @@ def read_smiles(path: str):
         return [line.strip() for line in f if line.strip()]
 
 
-def predict_all(model, tokenizer, smiles, batch_size: int, n_props: int = N_PROPS, predict=None) -> torch.Tensor:
-    """Normalised predictions [len(smiles), n_props] in INPUT order."""
+def predict_all(model, tokenizer, smiles, batch_size: int, n_props: int = N_PROPS, predict=None, host_tokenizer=False) -> torch.Tensor:
+    """Normalised predictions [len(smiles), n_props] in INPUT order.  host_tokenizer: --host_tokenizer (the Python tokenizer also where
+    the GPU could tokenise the file in one launch)."""
     if predict is None:
         from spmm_amd.decode import predict_properties as predict
-    rows = encode(tokenizer, smiles)
-    out = torch.empty(len(rows), n_props, dtype=torch.float32)
-    for idx in length_sorted_batches([len(r) for r in rows], batch_size):
-        ids, mask = pad_batch([rows[i] for i in idx], tokenizer.pad_token_id)
-        out[torch.from_numpy(idx)] = predict(model, ids, mask, n_props).float().cpu()      # (host mask: no device read sizes the batch)
+    lib = library_of(tokenizer, smiles, MAX_LENGTH, model, host_tokenizer)
+    out = torch.empty(len(lib), n_props, dtype=torch.float32)
+    for idx, ids, mask, n_tokens in lib.batches(batch_size):
+        kw = {"n_tokens": n_tokens} if lib.on_device else {}      # (host mask: counted there; device mask: the host's count goes along)
+        out[torch.from_numpy(idx)] = predict(model, ids, mask, n_props, **kw).float().cpu()
     return out
 
 
@@ -148,7 +150,7 @@ def main(args):
     model.eval()
     print("=" * 50)
     print("SMILES-to-PV generation...")
-    cand = predict_all(model, tokenizer, smiles, args.batch_size)
+    cand = predict_all(model, tokenizer, smiles, args.batch_size, host_tokenizer=args.host_tokenizer)
     print("SMILES-to-PV generation done")
     if args.reference_csv:
         ref = read_reference(args.reference_csv, len(smiles))
@@ -181,6 +183,7 @@ def parse_args(argv=None):
     p.add_argument("--seed", default=0, type=int, help="seed of --synthetic's weights and SMILES")
     p.add_argument("--synthetic", action="store_true", help="no data files: seeded weights, SMILES and vocabulary")
     p.add_argument("--tiny", action="store_true", help="2-layer / 128-d encoders (configs/config_bert_tiny.json)")
+    add_tokenizer_flags(p)
     return p.parse_args(argv)
 
 

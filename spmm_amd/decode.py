@@ -7,7 +7,7 @@ from __future__ import annotations
 import functools
 import math
 import random
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -1381,7 +1381,7 @@ class S2PDecoder:
     TP = "text_encoder.bert."
 
     @torch.no_grad()
-    def __init__(self, model, text_ids: torch.Tensor, text_mask: torch.Tensor, n_props: int = 53):
+    def __init__(self, model, text_ids: torch.Tensor, text_mask: torch.Tensor, n_props: int = 53, n_tokens: Optional[int] = None):
         from .engine import BF, host_token_count
         eng = model.engine
         eng.train_mode = False
@@ -1395,7 +1395,7 @@ class S2PDecoder:
         self.B, self.n_props, self.Lc, self.H = B, n_props, Lc, H
         # ---- the text, once: embeddings, packed rows, unimodal layers
         text = eng.encode_text(self.TP, ct, text_ids.to(dev).to(torch.int32).contiguous(), text_mask.to(dev).to(torch.int32).contiguous(),
-                               n_tokens=host_token_count(text_mask))
+                               n_tokens=host_token_count(text_mask) if n_tokens is None else int(n_tokens))      # (given: a device mask)
         # ---- cross-attention keys | values of every fusion layer, once
         proj = {f"{self.TP}encoder.layer.{l}.crossattention": KV for l, KV in _cross_kv(eng, self.TP, ct, text.y).items()}
         self.src = text.source(proj=proj)
@@ -1441,12 +1441,13 @@ class S2PDecoder:
 
 
 @torch.no_grad()
-def predict_properties(model, text_ids: torch.Tensor, text_mask: torch.Tensor, n_props: int = 53) -> torch.Tensor:
+def predict_properties(model, text_ids: torch.Tensor, text_mask: torch.Tensor, n_props: int = 53, n_tokens: Optional[int] = None) -> torch.Tensor:
     """`smiles_to_pv` (same arguments, same [B, n_props] normalised result) on the engine: S2PDecoder.  A model without an engine -- the
-    CPU oracle, any foreign module exposing the reference's sub-module API -- goes through `smiles_to_pv` itself."""
+    CPU oracle, any foreign module exposing the reference's sub-module API -- goes through `smiles_to_pv` itself.  n_tokens: the host's
+    count of valid tokens when the mask lives on the device (it sizes the packed text rows without a device read)."""
     if not hasattr(model, "engine"):
         return smiles_to_pv(model, text_ids, text_mask, n_props)
-    dec = S2PDecoder(model, text_ids, text_mask, n_props)
+    dec = S2PDecoder(model, text_ids, text_mask, n_props, n_tokens=n_tokens)
     for i in range(n_props):
         dec.step(i)
     return dec.pred

@@ -730,6 +730,29 @@ def smiles_mask(logits, tokens, table, *, t=0, t_last, k=1, mol=None, Lmax=None,
     return logits
 
 
+WORDPIECE_TABLE_MAX, WORDPIECE_CHARS_MAX, WORDPIECE_HEAD_MAX = 8192, 256, 16      # csrc/tokenize.hip
+
+
+def wordpiece(blob, offsets, table, head, ids, lens, status, *, gap, max_chars, max_pieces, unk_id, sep_id, pad_id):
+    """Device WordPiece in one launch (csrc/tokenize.hip, spmm_wordpiece; the host reference is tokenizer.encode_smiles, the table and the
+    host form of the walk are wordpiece_device.WordPieceTable): string i = the bytes blob[offsets[i] : offsets[i + 1] - gap) of the uint8
+    blob, offsets int64 [N + 1]; head uint8 [<= 16]: the text every word starts with; table int32 [<= 8192]: WordPieceTable.words.
+    ids int32 [N, >= max_pieces + 1], lens / status int32 [N]: every entry is written -- of a row-strided view of ids, the whole row stride
+    (padding beyond the view's columns).  All on one device."""
+    assert blob.dtype == torch.uint8 and blob.dim() == 1 and blob.is_contiguous()
+    assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 1
+    N = offsets.numel() - 1
+    assert head.dtype == torch.uint8 and head.dim() == 1 and head.is_contiguous() and head.numel() <= WORDPIECE_HEAD_MAX
+    assert table.dtype == torch.int32 and table.dim() == 1 and table.is_contiguous() and table.numel() <= WORDPIECE_TABLE_MAX
+    assert ids.dtype == torch.int32 and ids.dim() == 2 and ids.shape[0] == N and ids.shape[1] >= max_pieces + 1
+    assert all(t.dtype == torch.int32 and tuple(t.shape) == (N,) and t.is_contiguous() for t in (lens, status))
+    assert all(t.device == ids.device for t in (blob, offsets, table, head, lens, status))
+    assert 1 <= max_chars <= WORDPIECE_CHARS_MAX and max_pieces >= 1 and gap in (0, 1)
+    _call("spmm_wordpiece", _p(blob), _p(offsets), N, int(gap), _p(head), head.numel(), _p(table), table.numel(), int(max_chars),
+          int(max_pieces), int(unk_id), int(sep_id), int(pad_id), _p(ids), _row_stride(ids), _p(lens), _p(status), _st())
+    return ids
+
+
 def kv_prefill(K, V, row0, length, dst_row, Kc, Vc):
     """Whole prefixes into the decoder's self-attention cache (csrc/prefill.hip, spmm_kv_prefill): K / V bf16 [rows, nH*64] views of
     token-major rows with one row stride (the K and V column blocks of a fused Q|K|V projection); Kc / Vc bf16 [R, nH, Lmax, 64]

@@ -48,11 +48,13 @@ def _normalized(eng, proj: str, X: torch.Tensor, L: int, B: int, cls_rows=None) 
 
 
 @torch.no_grad()
-def smiles_features(model, ids: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
-    """text_feat of SPMM_models.py:93-95 for a batch of token ids [B, Lt] (position 0 = the '[CLS]' token) -> fp32 [B, E], unit rows."""
+def smiles_features(model, ids: torch.Tensor, mask: torch.Tensor, n_tokens: Optional[int] = None) -> torch.Tensor:
+    """text_feat of SPMM_models.py:93-95 for a batch of token ids [B, Lt] (position 0 = the '[CLS]' token) -> fp32 [B, E], unit rows.
+    n_tokens: the host's count of the mask's ones, for a mask that lives on the device (wordpiece_device.TokenLibrary.batches): sizes the
+    packed rows without a device read.  Absent, a host mask is counted here, as before."""
     eng = _engine(model)
     t = eng.encode_text(TP, model.cfg.text, ids.to(eng.dev).to(torch.int32).contiguous(), mask.to(eng.dev).to(torch.int32).contiguous(),
-                        n_tokens=host_token_count(mask))
+                        n_tokens=host_token_count(mask) if n_tokens is None else int(n_tokens))
     return _normalized(eng, "text_proj", t.y, t.L, t.B, cls_rows=t.cls_rows)
 
 
@@ -111,7 +113,24 @@ class MoleculeIndex:
         return cls(feats, ids_h, mask_h, smiles)
 
     @classmethod
-    def build(cls, model, tokenizer, smiles: Sequence[str], batch_size: int = 256) -> "MoleculeIndex":
+    @torch.no_grad()
+    def from_library(cls, model, library, batch_size: int = 256, smiles=None) -> "MoleculeIndex":
+        """The index of a wordpiece_device.TokenLibrary (host or device rows): its length-sorted batches through `smiles_features`, the
+        features written back in input order; the host ids / mask the re-ranking stage and `save` keep are made once, for the library."""
+        eng = _engine(model)
+        feats = torch.empty(len(library), model.cfg.embed_dim, dtype=torch.float32, device=eng.dev)
+        for idx, ids, mask, n_tokens in library.batches(batch_size):
+            feats[torch.from_numpy(idx).to(eng.dev)] = smiles_features(model, ids, mask, n_tokens=n_tokens)
+        ids_h, mask_h = library.padded_host()
+        return cls(feats, ids_h, mask_h, smiles)
+
+    @classmethod
+    def build(cls, model, tokenizer, smiles: Sequence[str], batch_size: int = 256, tokenizer_device=None) -> "MoleculeIndex":
+        """tokenizer_device: the GPU that tokenises the library (wordpiece_device.encode_smiles_device: one launch, the ids stay on the
+        device); None: SmilesWordPiece on the host, as before.  The index is the same either way."""
+        if tokenizer_device is not None:
+            from .wordpiece_device import TokenLibrary
+            return cls.from_library(model, TokenLibrary.from_strings(tokenizer, smiles, MAX_LENGTH, tokenizer_device), batch_size, smiles=list(smiles))
         rows = encode_smiles(tokenizer, smiles)
         ids, mask = pad_rows(rows, tokenizer.pad_token_id)
         return cls.from_tokens(model, ids, mask, batch_size, smiles=list(smiles))
