@@ -87,6 +87,15 @@ long spmm_gemm_tn_workspace_bytes(int M, int N, int K, int splits);
 /* kernel (per call): 0 = chosen from the shape; 1 = 128x128 tiles; 8 = 256x256 tiles on the 8-phase schedule (N, K % 8 == 0).
  * spmm_gemm_tn_splits returns the split count that fills the chip for that choice (pass the same `kernel` to both). */
 int spmm_gemm_tn_splits(int M, int N, int K, int kernel);
+/* Refused before any launch (SPMM_ERR_SHAPE): a null A, B or C; ldc < K (as spmm_gemm_tn_reduce refuses it); the alignment rules (N, K,
+ * ldc multiples of 4; lda, ldb multiples of 8 that cover the 8-column chunks of N / K; A, B 16-byte aligned).
+ * Row slicing of the 8-phase kernel (M >= 128; below that the 128x128 kernel runs): slices of rs = ceil(ceil(M / 128) / splits) * 128 rows,
+ * ns = ceil(M / rs) of them (ns <= splits).  With over = ns * rs - M, the LAST slice is the rlast = rs - (over / 128) * 128 rows that end at
+ * row M, and its first ndup = over % 128 rows, which the slice before also holds, are masked.  A single slice (ns == 1) takes the
+ * rlast = (M / 128) * 128 rows that end at row M, and the 128x128 kernel adds the first M % 128 rows in a pass of its own.
+ * With a device-side row count M_dev, a single slice or M < 256 runs on the 128x128 kernel at any `splits` (the device-side re-cut of the
+ * slices runs over no fewer than 256 rows, so it needs operands of at least 256 rows); otherwise the slices are re-cut on the device by
+ * the same rule, and slices left without rows contribute zero. */
 int spmm_gemm_tn(const void* A, long lda, const void* B, long ldb, int M, int N, int K, int splits, float alpha, float* C,
                  long ldc, float* workspace, int kernel, const int* M_dev, spmm_stream_t stream);
 /* C[n*ldc + k] += sum over ns slabs of N*K floats in `ws`: the split reduction spmm_gemm_tn runs itself, as an entry of its own. */

@@ -646,8 +646,10 @@ static void tn_reduce_launch(const float* ws, int ns, int N, int K, float* C, lo
 
 static int tn_run(const void* A, long lda, const void* B, long ldb, int M, int N, int K, int splits, float alpha, float* C, long ldc,
                   float* workspace, int kernel, const int* M_dev, hipStream_t stream) {
+  SPMM_CHECK_SHAPE(A != nullptr && B != nullptr && C != nullptr, "spmm_gemm_tn: null A / B / C");
   SPMM_CHECK_SHAPE(M > 0 && N > 0 && K > 0, "spmm_gemm_tn: empty problem M=%d N=%d K=%d", M, N, K);
   SPMM_CHECK_SHAPE(N % 4 == 0 && K % 4 == 0 && ldc % 4 == 0, "spmm_gemm_tn: N=%d K=%d ldc=%ld must be multiples of 4", N, K, ldc);
+  SPMM_CHECK_SHAPE(ldc >= K, "spmm_gemm_tn: ldc=%ld is shorter than a row of K=%d", ldc, K);
 #ifndef P8_PROFILE   // (the profiling build of tools/ aliases all rows onto row 0 with lda = ldb = 0: cache-resident operands)
   SPMM_CHECK_SHAPE(lda % 8 == 0 && ldb % 8 == 0 && lda >= ((N + 7) & ~7) && ldb >= ((K + 7) & ~7),
                    "spmm_gemm_tn: lda=%ld / ldb=%ld must be multiples of 8 covering the 8-column chunks of N=%d / K=%d", lda, ldb, N, K);
@@ -684,7 +686,9 @@ static int tn_run(const void* A, long lda, const void* B, long ldb, int M, int N
     if (ns == 1) { p.rlast = ((M + 127) / 128) * 128 > M ? (M / 128) * 128 : M; p.ndup = 0; }   // a single slice cannot overlap anything
     const int single_left = ns == 1 ? M - p.rlast : 0;
     dim3 grid(((N + 255) / 256) * ((K + 255) / 256) * ns, 1, 1);
-    if (M_dev != nullptr && ns == 1) {                 // one slice + remainder pass: the 128x128 kernel serves a device-side row count at any M
+    // One slice + remainder pass: the 128x128 kernel serves a device-side row count at any M.  So it does below 256 rows, whatever
+    // `splits` is: the device re-cut runs over no fewer than 256 rows, and its second slice would stage rows [M, 256) -- past the operands.
+    if (M_dev != nullptr && (ns == 1 || M < 256)) {
       p.nsplit = 0; p.M_ptr = M_dev;
       p.rsplit = ((M + BR - 1) / BR) * BR;
       hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(((N + BT - 1) / BT) * ((K + BT - 1) / BT), 1, 1), dim3(256), 0, stream, p);

@@ -165,6 +165,67 @@ def test_gemm_nt_refuses_what_its_fp32_epilogues_do_not_support(built, i):
     assert "spmm_gemm_nt failed (rc=1)" in str(e.value) and "launch failed" not in str(e.value), str(e.value)
 
 
+def _gemm_tn_args(A=P_, lda=256, B=P_, ldb=256, M=512, N=256, K=256, splits=1, C=P_, ldc=256, ws=P_, kernel=0):
+    return (A, lda, B, ldb, M, N, K, splits, 1.0, C, ldc, ws, kernel, None, None)
+
+
+GEMM_TN_REFUSED = (
+    [(_gemm_tn_args(**{k: None}), "spmm_gemm_tn: null A / B / C") for k in ("A", "B", "C")]
+    + [(_gemm_tn_args(**{k: 0}), "spmm_gemm_tn: empty problem") for k in ("M", "N", "K")]
+    + [(_gemm_tn_args(M=-5), "spmm_gemm_tn: empty problem M=-5"),
+       (_gemm_tn_args(N=254), "N=254 K=256 ldc=256 must be multiples of 4"),
+       (_gemm_tn_args(K=254), "N=256 K=254 ldc=256 must be multiples of 4"),
+       (_gemm_tn_args(ldc=258), "N=256 K=256 ldc=258 must be multiples of 4"),
+       (_gemm_tn_args(ldc=252), "spmm_gemm_tn: ldc=252 is shorter than a row of K=256"),
+       (_gemm_tn_args(lda=260), "lda=260 / ldb=256 must be multiples of 8"),
+       (_gemm_tn_args(ldb=260), "lda=256 / ldb=260 must be multiples of 8"),
+       (_gemm_tn_args(lda=248), "lda=248 / ldb=256 must be multiples of 8 covering"),
+       (_gemm_tn_args(ldb=248), "lda=256 / ldb=248 must be multiples of 8 covering"),
+       (_gemm_tn_args(N=252, lda=252), "lda=252 / ldb=256 must be multiples of 8 covering"),     # the last chunk of N = 252 ends at 256
+       (_gemm_tn_args(A=P_ + 8), "spmm_gemm_tn: A/B must be 16-B aligned"),
+       (_gemm_tn_args(B=P_ + 2), "spmm_gemm_tn: A/B must be 16-B aligned")]
+    + [(_gemm_tn_args(kernel=k), rf"spmm_gemm_tn: unknown kernel selector {k}") for k in (2, 9, -1)]
+    + [(_gemm_tn_args(kernel=8, N=260, lda=264), "the 8-phase kernel needs N % 8 == 0 and K % 8 == 0"),
+       (_gemm_tn_args(kernel=8, K=260, ldb=264, ldc=260), "the 8-phase kernel needs N % 8 == 0 and K % 8 == 0")]
+    + [(_gemm_tn_args(splits=2, ws=None, kernel=k), "spmm_gemm_tn: split reduction needs a workspace") for k in (0, 1, 8)]
+    + [(_gemm_tn_args(kernel=8, M=1 << 21, N=1024, K=256, lda=1024), "32-bit byte offsets"),
+       (_gemm_tn_args(kernel=8, M=1 << 21, N=256, K=1024, ldb=1024, ldc=1024), "32-bit byte offsets"),
+       (_gemm_tn_args(kernel=0, M=1 << 21, N=1024, K=256, lda=1024), "32-bit byte offsets")])
+
+
+@pytest.mark.parametrize("i", range(len(GEMM_TN_REFUSED)))
+def test_gemm_tn_refuses_incomplete_calls(built, i):
+    """Every check of spmm_gemm_tn, one call each that is complete but for the thing named: a null A, B or C, an empty problem, N / K / ldc
+    that break the 16-byte stores, ldc shorter than a row, lda / ldb that break or do not cover the 16-byte chunks, a misaligned operand,
+    an unknown kernel, the 8-phase kernel with N or K % 8 != 0, a split without a workspace, operands past the 8-phase kernel's 32-bit
+    offsets: each a SHAPE error (rc = 1) before any launch -- the pointers are dummies."""
+    from spmm_amd._lib import lib
+    args, msg = GEMM_TN_REFUSED[i]
+    with pytest.raises(RuntimeError, match=msg) as e:
+        lib().call("spmm_gemm_tn", *args)
+    assert "spmm_gemm_tn failed (rc=1)" in str(e.value) and "launch failed" not in str(e.value), str(e.value)
+
+
+def test_gemm_tn_workspace_and_split_count(built):
+    """spmm_gemm_tn_workspace_bytes = splits * N * K * 4 for splits > 1, else 0; spmm_gemm_tn_splits >= 1 at every case of the edge tests,
+    and 1 below 2048 rows (at least 16 reduction steps per slice: the training step never reaches the short-M slicing the edge tests force)."""
+    import gemm_tn_reference as G
+    from spmm_amd._lib import lib
+    c = lib().cdll
+    for (M, N, K) in ((641, 256, 256), (1000, 300, 132), (1, 4, 4), (16384, 768, 768)):
+        assert [c.spmm_gemm_tn_workspace_bytes(M, N, K, s) for s in (-1, 0, 1)] == [0, 0, 0]
+        for s in (2, 3, 7, 256):
+            assert c.spmm_gemm_tn_workspace_bytes(M, N, K, s) == s * N * K * 4
+    for p in G.ALL_CASES:
+        for kernel in (p.kernel, 0):
+            assert c.spmm_gemm_tn_splits(p.M, p.N, p.K, kernel) == 1, p.name
+    assert all(p.M < 2048 for p in G.ALL_CASES)
+    for (M, N, K), forced in G.CASES_AUTO:
+        assert c.spmm_gemm_tn_splits(M, N, K, 0) == c.spmm_gemm_tn_splits(M, N, K, forced) >= 1
+    assert c.spmm_gemm_tn_splits(2047, 768, 768, 8) == 1 and c.spmm_gemm_tn_splits(2048, 768, 768, 8) == 2
+    assert c.spmm_gemm_tn_splits(2047, 768, 768, 1) == 1 and c.spmm_gemm_tn_splits(2048, 768, 768, 1) == 2
+
+
 def test_product_refuses_to_run_without_the_extension(tmp_path):
     """No CPU / eager fallback: with the shared library missing the library handle and the ops that reach it raise and name the file
     they looked for (ops that take a stream fail even earlier on a box without a GPU: torch reports the missing device)."""
