@@ -563,6 +563,48 @@ int spmm_rows_linear(const void* x, int x_is_bf16, long ldx, const float* W, con
 long spmm_sim_topk_workspace_bytes(int Q, long n, int k);
 int spmm_sim_topk(const float* q, long ldq, const float* f, long ldf, long base, int Q, long n, int E, int k, float* scores, long* index,
                   int merge, const float* cut_scores, const long* cut_index, void* workspace, long workspace_bytes, spmm_stream_t stream);
+/* Library clustering (csrc/cluster.hip): spherical k-means and farthest-first picks on the features spmm_sim_topk searches.
+ *
+ * spmm_centroid_assign: the nearest centre of every row, streamed -- the [n, Kc] similarity matrix is never formed.  f: fp32 [n, E], row
+ * stride ldf; c: fp32 [Kc, E], row stride ldc, ONE CHUNK of a centre list whose row j has the centre index c0 + j.  State (in/out): best
+ * fp32 [n] and assign int32 [n].
+ *   merge = 0: the state is overwritten with the chunk's best centre;  merge = 1: the state already there competes as one more candidate
+ *   (centre lists processed in chunks; with Kc = 1, one step of farthest-first traversal: best becomes the similarity to the nearest pick).
+ * Contract: candidates are ordered exactly as spmm_sim_topk orders them -- larger score first, equal scores by ascending centre index, NaN
+ * below every number, -0 and +0 equal (returned as +0); with merge = 1 a state of (-inf, -1) is the empty slot (any assign < 0 is).  The
+ * score of (row, centre) is that kernel's accumulator chain (v_mfma_f32_16x16x4_f32; 16-element step ascending, then component, then lane
+ * group), so best / assign are bit-identical to spmm_sim_topk(q = f, f = c, k = 1, base = c0, merge), for any chunking of the centres; two
+ * launches on the same inputs agree bit for bit.  No workspace, no floating-point atomics.
+ * prev int32 [n] / changed (device int), optional, both or neither: *changed += the number of rows whose final assign differs from prev
+ * (an integer atomic: the count is deterministic).  prev must not alias assign.
+ * Limits, reported as bad arguments: E a multiple of 64 up to 512; Kc >= 1; c0 >= 0 and c0 + Kc <= 2^31 - 1; 0 <= n <= 2^31 - 256 (n = 0 is a
+ * no-op); f, c 16-byte aligned; ldf, ldc multiples of 4, at least E; merge 0 or 1. */
+int spmm_centroid_assign(const float* f, long ldf, const float* c, long ldc, long c0, long n, int Kc, int E, float* best, int* assign,
+                         int merge, const int* prev, int* changed, spmm_stream_t stream);
+/* spmm_cluster_group: the members of every cluster, a stable counting sort of the rows by assign int32 [n].  counts int32 [K]; offsets int64
+ * [K + 1] (offsets[0] = 0, offsets[K] = the number of rows in a cluster); members int32 [n]: the rows of cluster c are
+ * members[offsets[c] : offsets[c + 1]] in ASCENDING row order (entries past offsets[K] are not written).  A row whose assign is outside
+ * [0, K) -- -1, the empty slot -- is in no cluster; *outside (device int, overwritten) counts those rows.  Integer atomics only: the result
+ * does not depend on the grid.  workspace: spmm_cluster_group_workspace_bytes(n, K) bytes, 16-byte aligned, private to the call.
+ * Limits, reported as bad arguments: 1 <= K <= 2^24; 0 <= n <= 2^31 - 256. */
+long spmm_cluster_group_workspace_bytes(long n, int K);
+int spmm_cluster_group(const int* assign, long n, int K, int* counts, long* offsets, int* members, int* outside, void* workspace,
+                       long workspace_bytes, spmm_stream_t stream);
+/* spmm_cluster_centroids: per cluster c of a grouping (counts / offsets / members of spmm_cluster_group over f fp32 [n, E], row stride ldf):
+ *   the fp32 sum of its members' rows, in an order fixed by the member list alone -- pieces of 256 consecutive members summed in member
+ *   order, the piece sums added in ascending order (a 500 000-member cluster is 1 954 workgroups and one combining pass, not one chain);
+ *   norm[c] fp32 = the length of that sum (0 for an empty cluster);
+ *   centres[c, :] (fp32, row stride ldc) = sum / norm, written ONLY when the cluster has members and norm >= 1e-12: otherwise the row is
+ *   left as it was (spherical k-means keeps the old centre of an empty or cancelled cluster until the host re-seeds it);
+ *   medoid[c] int32 = the member with the largest best[row] in spmm_sim_topk's score order (NaN lowest, -0 = +0), ties to the lowest row;
+ *   -1 for an empty cluster.
+ * No floating-point atomics; two launches on the same inputs agree bit for bit.  workspace: spmm_cluster_centroids_workspace_bytes(n, K, E)
+ * bytes, 16-byte aligned, private to the call.  Limits, reported as bad arguments: 1 <= E <= 512; 1 <= K <= 2^24; 0 <= n <= 2^31 - 256;
+ * ldf, ldc at least E. */
+long spmm_cluster_centroids_workspace_bytes(long n, int K, int E);
+int spmm_cluster_centroids(const float* f, long ldf, long n, int E, const float* best, const int* counts, const long* offsets,
+                           const int* members, int K, float* centres, long ldc, float* norm, int* medoid, void* workspace,
+                           long workspace_bytes, spmm_stream_t stream);
 /* _dequeue_and_enqueue SPMM_models.py:272-286 (+ the bf16 GEMM shadows of the queue).  skip_flag (optional, device int): when
  * non-zero neither the queue nor the pointer is touched -- the reference's NaN guard returns before the enqueue
  * (SPMM_models.py:132-134 vs :208), so a non-finite momentum feature never enters the queue. */

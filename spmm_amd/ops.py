@@ -521,6 +521,64 @@ def sim_topk(q, f, scores, index, *, base=0, merge=False, cut=None, ws=None):
     return scores, index
 
 
+def centroid_assign(f, c, best, assign, *, c0=0, merge=False, prev=None, changed=None):
+    """Nearest centre of every row of f [n, E] among one chunk c [Kc, E] of a centre list (csrc/cluster.hip): the state best fp32 [n] /
+    assign int32 [n] is overwritten (merge False) or competes as one more candidate (merge True); centre index of chunk row j = c0 + j.
+    prev int32 [n] / changed int32 [1]: changed += the rows whose final assign differs from prev."""
+    n, E = f.shape
+    Kc = c.shape[0]
+    assert f.dtype == torch.float32 and c.dtype == torch.float32 and c.shape[1] == E
+    assert best.dtype == torch.float32 and assign.dtype == torch.int32 and best.numel() == assign.numel() == n
+    assert best.is_contiguous() and assign.is_contiguous()
+    assert (prev is None) == (changed is None)
+    assert prev is None or (prev.dtype == torch.int32 and prev.numel() == n and prev.is_contiguous() and changed.dtype == torch.int32
+                            and prev.data_ptr() != assign.data_ptr())
+    _call("spmm_centroid_assign", _p(f) if n > 0 else None, _row_stride(f) if n > 0 else E, _p(c), _row_stride(c), int(c0), n, Kc, E, _p(best),
+          _p(assign), int(bool(merge)), _p(prev), _p(changed), _st())
+    return best, assign
+
+
+def cluster_group(assign, K, counts, offsets, members, outside, ws=None):
+    """Members of every cluster (csrc/cluster.hip): counts int32 [K], offsets int64 [K + 1], members int32 [n] -- cluster c's rows are
+    members[offsets[c]:offsets[c + 1]], ascending; outside int32 [1] = the rows whose assign is not in [0, K)."""
+    n = assign.numel()
+    assert assign.dtype == torch.int32 and assign.is_contiguous() and counts.dtype == torch.int32 and counts.numel() == K and counts.is_contiguous()
+    assert offsets.dtype == torch.int64 and offsets.numel() == K + 1 and offsets.is_contiguous()
+    assert members.dtype == torch.int32 and members.numel() == n and members.is_contiguous() and outside.dtype == torch.int32
+    if ws is None:
+        ws = cluster_group_workspace(n, K, counts.device)
+    _call("spmm_cluster_group", _p(assign) if n > 0 else None, n, int(K), _p(counts), _p(offsets), _p(members) if n > 0 else None, _p(outside),
+          _p(ws), ws.numel(), _st())
+    return counts, offsets, members
+
+
+def cluster_group_workspace(n, K, device):
+    nbytes = 16 if _DRY_RUN else lib().cdll.spmm_cluster_group_workspace_bytes(int(n), int(K))
+    return torch.empty(max(16, nbytes), dtype=torch.uint8, device=device)
+
+
+def cluster_centroids_workspace(n, K, E, device):
+    nbytes = 16 if _DRY_RUN else lib().cdll.spmm_cluster_centroids_workspace_bytes(int(n), int(K), int(E))
+    return torch.empty(max(16, nbytes), dtype=torch.uint8, device=device)
+
+
+def cluster_centroids(f, best, counts, offsets, members, centres, norm, medoid, ws=None):
+    """Per cluster of a grouping of f [n, E]: centres[c] = sum of its rows / |sum| (left as it was for an empty cluster or |sum| < 1e-12),
+    norm fp32 [K] = |sum|, medoid int32 [K] = the member with the largest best (ties to the lowest row; -1 when empty).  Fixed order."""
+    n, E = f.shape
+    K = counts.numel()
+    assert f.dtype == torch.float32 and best.dtype == torch.float32 and best.numel() == n and best.is_contiguous()
+    assert counts.dtype == torch.int32 and offsets.dtype == torch.int64 and offsets.numel() == K + 1 and members.dtype == torch.int32
+    assert members.numel() == n and counts.is_contiguous() and offsets.is_contiguous() and members.is_contiguous()
+    assert centres.dtype == torch.float32 and tuple(centres.shape) == (K, E) and norm.dtype == torch.float32 and norm.numel() == K
+    assert medoid.dtype == torch.int32 and medoid.numel() == K and norm.is_contiguous() and medoid.is_contiguous()
+    if ws is None:
+        ws = cluster_centroids_workspace(n, K, E, f.device)
+    _call("spmm_cluster_centroids", _p(f) if n > 0 else None, _row_stride(f) if n > 0 else E, n, E, _p(best) if n > 0 else None, _p(counts),
+          _p(offsets), _p(members) if n > 0 else None, K, _p(centres), _row_stride(centres), _p(norm), _p(medoid), _p(ws), ws.numel(), _st())
+    return centres, norm, medoid
+
+
 def enqueue(feats, queue, w3, qT, ptr, *, Bloc, advance=True, skip_flag=None):
     n, E = feats.shape
     _call("spmm_enqueue", _p(feats), n, E, _p(queue), queue.shape[1], _p(w3), _p(qT), _row_stride(qT), Bloc, _p(ptr),
