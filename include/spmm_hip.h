@@ -211,7 +211,9 @@ int spmm_embed_step_ln_fwd(const int* ids, int pos_index, const int* pos_ptr, co
  * there (the table's entry for that position must name the row's own cache row: s(r, last) = r, or rowmap[r]), and the launch copies
  * them into that cache row for the positions to come, so the caller needs no cache-update copies of its own.  rowmap (optional, [R]):
  * the cache row row r's newest position goes to (s = rowmap[r]) -- after the caller dropped finished molecules from its batch, the
- * rows it still decodes keep writing to the cache rows their ancestry tables name. */
+ * rows it still decodes keep writing to the cache rows their ancestry tables name.
+ * Refused before a launch: strides that are no multiples of 8; 255 * tok_stride >= 2^31 (the kernels form j * tok_stride in 32 bits); q, K,
+ * V, knew or vnew not 16-byte aligned, out not 8-byte aligned; a null q, K, V or out. */
 int spmm_decode_attn(const void* q, long ldq, const void* K, const void* V, long seq_stride, long tok_stride, long head_stride, const int* anc,
                      int anc_ld, int kv_div, int group, void* out, long ldo, int R, int nH, int Lkv, float scale,
                      const int* t_ptr, const void* knew, const void* vnew, long ldn, const int* rowmap, spmm_stream_t stream);

@@ -417,6 +417,10 @@ extern "C" int spmm_decode_attn(const void* q, long ldq, const void* K, const vo
   SPMM_CHECK_SHAPE(seq_stride % 8 == 0 && tok_stride % 8 == 0 && ldq >= (long)nH * 64 && ldo >= (long)nH * 64 && ldq % 8 == 0 && ldo % 8 == 0,
                    "spmm_decode_attn: strides must keep 16-B alignment (seq %ld tok %ld)", seq_stride, tok_stride);
   SPMM_CHECK_SHAPE(group > 0 && R % group == 0, "spmm_decode_attn: R=%d must be a multiple of group=%d", R, group);
+  SPMM_CHECK_SHAPE(tok_stride >= 0 && tok_stride * 255 < (1L << 31), "spmm_decode_attn: tok_stride=%ld (0 <= 255 * tok_stride < 2^31)", tok_stride);
+  SPMM_CHECK_SHAPE(q != nullptr && K != nullptr && V != nullptr && out != nullptr, "spmm_decode_attn: q, K, V and out are required");
+  SPMM_CHECK_SHAPE((((uintptr_t)q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)knew | (uintptr_t)vnew) & 15) == 0 && ((uintptr_t)out & 7) == 0,
+                   "spmm_decode_attn: misaligned pointer (q, K, V, knew, vnew: 16 bytes; out: 8)");
   const long waves = (long)R * nH;
   const int nblocks = (int)((waves + 3) / 4);
   DecAttnP p = {(const bf16*)q, ldq, (const bf16*)K, (const bf16*)V, seq_stride, tok_stride, head_stride, anc, anc_ld, kv_div, group, nblocks,
