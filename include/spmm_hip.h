@@ -43,7 +43,15 @@ const char* spmm_last_error(void);
 #define SPMM_EPI_F32_ACC 5     /* C(f32) += alpha*acc/(*div) + bias + R   (plain read-modify-write, single owner) */
 #define SPMM_EPI_GELU_DERIV 6  /* pre = acc + bias ; C(bf16) = gelu_erf(pre) ; C2(bf16) = gelu_erf'(pre): the FFN forward keeps  */
                                /* the derivative (one shared exp) so that the backward epilogue is SPMM_EPI_MUL                  */
-#define SPMM_EPI_MUL 7         /* C(bf16) = alpha*acc * G      (G bf16, e.g. the stored gelu'; colsum allowed)                   */
+#define SPMM_EPI_MUL 7         /* C(bf16) = (alpha*acc/(*div) + bias) * G   (G bf16, e.g. the stored gelu'; colsum allowed)      */
+/* The five bf16-output epilogues (BF16, GELU, GELU_GRAD, GELU_DERIV, MUL) share pre = alpha*acc/(*div) + bias, in fp32: bias, alpha and *div
+ * apply under every one of them -- SPMM_EPI_MUL stores (pre) * G and SPMM_EPI_GELU_GRAD (pre) * gelu_erf'(G), so a bias is added BEFORE the
+ * multiplication (the step passes none there).  Rounding: gelu_erf(pre), gelu_erf'(pre) and pre of the two GELU forms are computed from the
+ * fp32 pre and rounded to bf16 once.  An epilogue with a second operand rounds TWICE: pre is rounded to bf16 (the tile image the stores are
+ * read from), then R is added (SPMM_EPI_BF16), or G / gelu_erf'(G) multiplied, in fp32 and the result is rounded to bf16 again -- on every
+ * kernel alike.  colsum[n] += the sum, over the rows computed (*M_dev of them under a device-side row count), of the bf16 values stored
+ * to C, in fp32 with atomics: it adds to what colsum holds.  C2 of SPMM_EPI_GELU / _GELU_DERIV is optional (null = not kept).
+ * tests/gemm_bf16_reference.py holds the float64 reference and the error bound that follows from these rounding points. */
 /* The three fp32-output epilogues take bias (fp32 [N]) and R (bf16 [M, ldr], ldr % 4 == 0, 8-B aligned) like SPMM_EPI_BF16; acc is the
  * whole K reduction: under split-K (SPMM_EPI_F32_ATOMIC, splits > 1) every K-slice adds alpha/(*div) times its partial sum and bias and
  * R are added exactly ONCE per element (by the first slice), whatever `splits` is. */
