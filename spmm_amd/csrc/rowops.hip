@@ -181,8 +181,8 @@ __global__ __launch_bounds__(256) void ln_fwd16_kernel(const bf16* __restrict__ 
   const int l32 = threadIdx.x & 31;
   if (rows_ptr) {                                  // device-side row count (<= rows): workgroups wholly past it leave at once
     const long r_ = *rows_ptr;
-    rows = r_ < rows ? (r_ > 0 ? r_ : 1) : rows;
-    if ((long)blockIdx.x * 8 >= rows) return;
+    rows = r_ < rows ? r_ : rows;
+    if ((long)blockIdx.x * 8 >= rows) return;      // (a count of 0 leaves here too: `rows - 1` below is only formed for rows >= 1)
   }
   long row = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
   const bool live = row < rows;
