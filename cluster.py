@@ -6,11 +6,16 @@ retrieve.py takes them:
   python cluster.py ... --library library.txt --save_index library.idx     (encode the library once ...)
   python cluster.py --index library.idx --pick 500 --output picks.csv      (... and organise it many times; no model is needed then)
   python cluster.py --synthetic 300 --tiny --k 5                           (no data files: seeded weights, library, vocabulary)
+  python cluster.py --index library.idx --threshold 0.8 --output clusters.csv --medoids leaders.txt      (Butina: the threshold gives K)
+  python cluster.py --index library.idx --dedup 0.98 --output unique.csv                                   (drop near-duplicates)
 
 --k K clusters the library by spherical k-means on the text features (spmm_amd.cluster.kmeans): the CSV has one row per molecule --
 library line (1-based), SMILES, cluster, cosine to the cluster's centre, whether it is the cluster's medoid; --medoids FILE lists one
 representative per cluster.  --pick N picks N molecules as unlike each other as possible (MaxMin picking, spmm_amd.cluster.pick_diverse):
-the CSV has one row per pick in picking order with its largest cosine to the earlier picks."""
+the CSV has one row per pick in picking order with its largest cosine to the earlier picks.  --threshold T clusters by leaders instead
+(spmm_amd.cluster.leaders: Taylor-Butina with --order count, first-come leaders with --order row): every molecule within T of its cluster's
+leader, no two leaders within T of each other; the same CSV with the leader in the medoid's place and a column n_neighbours.  --dedup T
+writes the molecules that are not within T of an earlier kept one."""
 import argparse
 import csv
 import os
@@ -46,6 +51,23 @@ def medoid_rows(counts, medoid, smiles):
             for c, (n, m) in enumerate(zip(counts.tolist(), medoid.tolist()))]
 
 
+def leader_rows(cluster, cosine, leader, n_neighbours, smiles):
+    """A leader clustering -> cluster_rows' columns (the cosine is to the leader, is_medoid marks the leader) and the neighbour count."""
+    return [(i + 1, smiles[i] if smiles is not None else "", int(c), repr(float(b)), int(l == i), int(d))
+            for i, (c, b, l, d) in enumerate(zip(cluster.tolist(), cosine.tolist(), leader.tolist(), n_neighbours.tolist()))]
+
+
+def dedup_rows(leader, smiles):
+    """-> (kept [(library line, SMILES)], dropped [(library line, the line it was folded into)])."""
+    kept, dropped = [], []
+    for i, l in enumerate(leader.tolist()):
+        if l == i:
+            kept.append((i + 1, smiles[i] if smiles is not None else ""))
+        else:
+            dropped.append((i + 1, l + 1))
+    return kept, dropped
+
+
 def write_csv(path: str, header, rows):
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
@@ -56,6 +78,8 @@ def write_csv(path: str, header, rows):
 CLUSTER_HEADER = ["library_line", "smiles", "cluster", "cosine_to_centre", "is_medoid"]
 PICK_HEADER = ["pick_order", "library_line", "smiles", "max_cosine_to_earlier_picks"]
 MEDOID_HEADER = ["cluster", "size", "library_line", "smiles"]
+LEADER_HEADER = CLUSTER_HEADER + ["n_neighbours"]
+DEDUP_HEADER = ["library_line", "smiles"]
 
 
 def check_size(args, N: int):
@@ -68,9 +92,19 @@ def check_size(args, N: int):
 
 def check_args(args):
     """What can be refused before a model is built -> the library's SMILES when they are read here (None for --index)."""
+    by_threshold, by_dedup = args.threshold is not None, args.dedup is not None
+    if by_threshold and args.k:
+        raise SystemExit("--threshold and --k are alternatives: the threshold decides the number of clusters")
+    if (by_threshold or by_dedup) and (args.k or args.pick or (by_threshold and by_dedup)):
+        raise SystemExit("--k, --pick, --threshold and --dedup are alternatives")
+    for name, t in (("--threshold", args.threshold), ("--dedup", args.dedup)):
+        if t is not None and not -1.0 <= t <= 1.0:
+            raise SystemExit(f"{name} {t} is not a cosine in [-1, 1]")
+    if args.max_pairs < 0:
+        raise SystemExit("--max_pairs must be at least 0")
     if args.k and args.pick:
         raise SystemExit("--k and --pick are alternatives: cluster the library, or pick a diverse subset of it")
-    if not args.k and not args.pick:
+    if not args.k and not args.pick and not by_threshold and not by_dedup:
         raise SystemExit("give --k K (cluster the library) or --pick N (pick a diverse subset)")
     if args.k < 0 or args.k > MAX_K:
         raise SystemExit(f"--k {args.k} outside [1, {MAX_K}]")
@@ -78,8 +112,8 @@ def check_args(args):
         raise SystemExit(f"--pick {args.pick} must be at least 1")
     if args.iters < 1:
         raise SystemExit("--iters must be at least 1")
-    if args.medoids and not args.k:
-        raise SystemExit("--medoids goes with --k")
+    if args.medoids and not (args.k or by_threshold):
+        raise SystemExit("--medoids goes with --k or --threshold")
     if not args.synthetic and not (args.library or args.index):
         raise SystemExit("give the library: --library FILE (one SMILES per line) or --index FILE (saved by --save_index)")
     if args.library and args.index:
@@ -97,6 +131,40 @@ def check_args(args):
 def size_summary(counts):
     s = sorted(counts.tolist())
     return s[0], s[len(s) // 2], s[-1]
+
+
+def main_leaders(args, index, C):
+    """--threshold / --dedup on an encoded library."""
+    dedup = args.dedup is not None
+    try:
+        res = C.leaders(index, args.dedup if dedup else args.threshold, order="row" if dedup else args.order, max_pairs=args.max_pairs)
+    except ValueError as e:
+        raise SystemExit(f"cluster.py: {e}")
+    N = len(index)
+    degree = res.n_neighbours.cpu()
+    print(f"{res.pairs // 2} pairs at or above {res.threshold!r}: mean degree {res.pairs / max(N, 1):.2f}, max degree "
+          f"{int(degree.max()) if N else 0}; {res.rounds} rounds")
+    if dedup:
+        kept, dropped = dedup_rows(res.leader.cpu(), index.smiles)
+        write_csv(args.output, DEDUP_HEADER, kept)
+        for line, into in dropped:
+            print("line %-8d dropped: a duplicate of line %d" % (line, into))
+        print(f"{len(dropped)} of {N} lines dropped; {len(kept)} molecules are saved in '{args.output}'")
+        return kept
+    counts, lead = res.counts.cpu(), res.leaders.cpu()
+    print(f"{counts.numel()} clusters (order {res.order}), {int((counts == 1).sum())} singletons")
+    if counts.numel():
+        print("cluster sizes: min %d, median %d, max %d" % size_summary(counts))
+    meds = medoid_rows(counts, lead, index.smiles)
+    for c, n, line, smi in sorted(meds, key=lambda r: (-r[1], r[0]))[:10]:
+        print("cluster %-6d size %-8d leader line %-8s %s" % (c, n, line, smi))
+    out = leader_rows(res.cluster.cpu(), res.cosine_to_leader.cpu(), res.leader.cpu(), degree, index.smiles)
+    write_csv(args.output, LEADER_HEADER, out)
+    print(f"{len(out)} molecules are saved in '{args.output}'")
+    if args.medoids:
+        write_csv(args.medoids, MEDOID_HEADER, meds)
+        print(f"{len(meds)} clusters are saved in '{args.medoids}'")
+    return out
 
 
 def main(args):
@@ -146,7 +214,9 @@ def main(args):
         index.save(args.save_index)
         print(f"Index saved in '{args.save_index}'")
     print("=" * 50)
-    if args.pick:
+    if args.threshold is not None or args.dedup is not None:
+        out = main_leaders(args, index, C)
+    elif args.pick:
         rows, sim = C.pick_diverse(index, args.pick, seed=args.seed)
         out = pick_rows(rows.cpu(), sim.cpu(), index.smiles)
         write_csv(args.output, PICK_HEADER, out)
@@ -189,10 +259,18 @@ def parse_args(argv=None):
     p.add_argument("--iters", default=20, type=int, help="k-means iterations at the most")
     p.add_argument("--init", default="farthest", choices=("farthest", "random"), help="initial centres: farthest-first traversal, or random rows")
     p.add_argument("--pick", default=0, type=int, metavar="N", help="pick N molecules as unlike each other as possible instead of clustering")
+    p.add_argument("--threshold", default=None, type=float, metavar="T",
+                   help="cluster by leaders instead: every molecule within cosine T of its cluster's leader (the number of clusters is a result)")
+    p.add_argument("--order", default="count", choices=("count", "row"),
+                   help="with --threshold: 'count' = Taylor-Butina (the most neighbours lead first, ties to the lower line), 'row' = first come")
+    p.add_argument("--dedup", default=None, type=float, metavar="T",
+                   help="write the molecules that are not within cosine T of an earlier kept one (library_line, smiles)")
+    p.add_argument("--max_pairs", default=1 << 30, type=int, help="refuse a neighbour list with more entries than this (4 bytes each)")
     p.add_argument("--output", default="clustered_molecules.csv",
                    help="CSV: library line, SMILES, cluster, cosine to its centre, is_medoid (--pick: pick order, library line, SMILES, "
                         "largest cosine to the earlier picks)")
-    p.add_argument("--medoids", default="", help="with --k: one line per cluster -- cluster, size, library line and SMILES of its medoid")
+    p.add_argument("--medoids", default="", help="with --k: one line per cluster -- cluster, size, library line and SMILES of its medoid "
+                                                 "(with --threshold: of its leader)")
     p.add_argument("--seed", default=0, type=int, help="seed of the first pick / the random centres, and of --synthetic's weights and library")
     p.add_argument("--synthetic", default=0, type=int, metavar="N", help="no data files: seeded weights and N made-up molecules")
     p.add_argument("--tiny", action="store_true", help="2-layer / 128-d encoders (configs/config_bert_tiny.json)")

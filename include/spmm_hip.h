@@ -615,6 +615,48 @@ long spmm_cluster_centroids_workspace_bytes(long n, int K, int E);
 int spmm_cluster_centroids(const float* f, long ldf, long n, int E, const float* best, const int* counts, const long* offsets,
                            const int* members, int K, float* centres, long ldc, float* norm, int* medoid, void* workspace,
                            long workspace_bytes, spmm_stream_t stream);
+/* Threshold clustering (csrc/neighbors.hip): every pair of library rows more similar than a threshold, and Taylor-Butina / first-come
+ * leaders on that list -- the number of clusters is a result, not an argument.
+ *
+ * spmm_sim_range: the neighbours of every row above `threshold`, streamed -- the [n, nc] similarity matrix is never formed.  f: fp32 [n, E],
+ * row stride ldf, the rows with the library indices r0 .. r0 + n - 1; c: fp32 [nc, E], row stride ldc, ONE CHUNK of the column side whose
+ * row j has the library index c0 + j (a self-join passes the same library on both sides).  State (in/out): counts int32 [n].
+ *   count mode (offsets = nbr = NULL, nbr_len = 0): counts[i] += the hits of row i in this chunk;
+ *   emit mode (offsets int64 [n], nbr int32 [nbr_len]): hit number p of row i in this chunk, p counted in ascending j, is written as c0 + j
+ *   to nbr[offsets[i] + counts[i] + p]; after that counts[i] += the hits.  A position outside [0, nbr_len) is not written and the count
+ *   still advances: a wrong offsets can lose entries but never writes outside nbr.
+ * Contract: (i, j) is a hit when score(i, j) >= threshold -- a float compare, so a NaN score never hits -- and r0 + i != c0 + j: the
+ * diagonal is never a neighbour, an exact copy elsewhere in the library is.  The score is the accumulator chain of spmm_sim_topk /
+ * spmm_centroid_assign (v_mfma_f32_16x16x4_f32; 16-element step ascending, then component, then lane group): bit-identical to those
+ * kernels', and score(i, j) has the bits of score(j, i), so the neighbour relation of a self-join is exactly symmetric.  Column chunks
+ * offered in ascending c0 give every row's list in ascending library index, and ANY chunking of the columns (or of the rows, with r0 and
+ * the matching slices of counts / offsets) gives the same bytes; two launches on the same inputs agree bit for bit.  A wave is the only
+ * writer of its rows' lists and counts: no atomics on nbr, no floating-point atomics, no sort, no workspace.
+ * Limits, reported as bad arguments: E a multiple of 64 up to 512; 0 <= n, nc <= 2^31 - 256 (either being 0 is a no-op); r0, c0 >= 0 and
+ * r0 + n, c0 + nc <= 2^31 - 1; threshold not NaN; f, c 16-byte aligned; ldf, ldc multiples of 4, at least E; offsets, nbr and nbr_len all
+ * given or none; nbr_len >= 0. */
+int spmm_sim_range(const float* f, long ldf, long r0, long n, const float* c, long ldc, long c0, long nc, int E, float threshold,
+                   int* counts, const long* offsets, int* nbr, long nbr_len, spmm_stream_t stream);
+/* spmm_leader_round / spmm_leader_finish: the leaders of a SYMMETRIC neighbour list (offsets int64 [n + 1], nbr int32 [nbr_len]: the
+ * neighbours of row i are nbr[offsets[i] : offsets[i + 1]]; entries outside [0, n) are ignored, positions outside [0, nbr_len) never read).
+ * The sequential rule: visit the rows in priority order; a row not yet claimed becomes a leader and claims its unclaimed neighbours.
+ * Priority: by_count = 1 (Taylor-Butina) more neighbours first -- counts int32 [n] -- equal counts to the LOWER row (RDKit's
+ * Butina.ClusterData gives equal counts to the higher index); by_count = 0 (leader / sphere exclusion: keep the first occurrence) the
+ * lower row first, counts may be NULL.  On a symmetric relation the leaders are the lexicographically first maximal independent set,
+ * which one round computes in parallel: state int32 [n] is 0 (open), 1 (leader) or 2 (member); an open row with a leader among its
+ * neighbours of higher priority becomes a member, one whose neighbours of higher priority are all members (or that has none) becomes a
+ * leader, any other stays open.  A round reads state_in and writes every row of state_out (they must be two buffers); *open_out (device
+ * int) += the rows still open, one integer atomic per wave.  Start from zeros and repeat until a round leaves no row open: every round
+ * decides at least the best open row; a path under row priority needs n rounds, a typical similarity graph a handful.
+ * spmm_leader_finish: leader[i] int32 = i for a leader, else the highest-priority leader among i's neighbours -- the one that claims it in
+ * the sequential run (-1 for a row that is neither: an open row, a member without a leader).  One wave64 per row, its lanes striding the
+ * list.  Integer-exact; two launches agree bit for bit.
+ * Refused as bad arguments: null pointers (counts only with by_count = 1), n outside [0, 2^31 - 256] (n = 0 is a no-op), nbr_len < 0,
+ * by_count other than 0 or 1, state_in == state_out. */
+int spmm_leader_round(const int* counts, const long* offsets, const int* nbr, long nbr_len, long n, int by_count, const int* state_in,
+                      int* state_out, int* open_out, spmm_stream_t stream);
+int spmm_leader_finish(const int* counts, const long* offsets, const int* nbr, long nbr_len, long n, int by_count, const int* state,
+                       int* leader, spmm_stream_t stream);
 /* _dequeue_and_enqueue SPMM_models.py:272-286 (+ the bf16 GEMM shadows of the queue).  skip_flag (optional, device int): when
  * non-zero neither the queue nor the pointer is touched -- the reference's NaN guard returns before the enqueue
  * (SPMM_models.py:132-134 vs :208), so a non-finite momentum feature never enters the queue. */

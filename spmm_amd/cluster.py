@@ -8,6 +8,8 @@ with the roles swapped: every library row asks which of K centres is nearest (cs
   kmeans        spherical k-means: assign -> group (spmm_cluster_group: members of every cluster, ascending) -> centroids
                 (spmm_cluster_centroids: fixed-order sums, norms, medoids); empty or cancelled clusters re-seeded from the worst-served rows
   pick_diverse  MaxMin picking = farthest-first traversal: one assign launch per pick with the one new centre and merge = 1
+  neighbours / leaders / dedup   threshold clustering (csrc/neighbors.hip), further down: every pair above a threshold, Taylor-Butina and
+                first-come leaders on that list -- the number of clusters is a result
 
 Deterministic: no floating-point atomics, every sum in an order fixed by the data; two runs agree bit for bit.  Inference only.
 `engine=False` is the tensor-library form of the same rules with float64 scores (runs on CPU tensors): the yard-stick of the tests and of
@@ -270,3 +272,220 @@ def kmeans(feats, k: int, iters: int = 20, init: str = "farthest", seed: int = 0
     return Clustering(centres=last["centres"], assign=last["assign"], best=last["best"], counts=last["counts"], offsets=last["offsets"],
                       members=last["members"], medoid=last["medoid"], objective=[s["stats"][2] for s in done], iterations=len(done),
                       reseeded=int(sum(s["stats"][1] for s in done)), changed=int(last["stats"][0]))
+
+
+# ------------------------------------------------------------------------------------------------------------------ threshold clustering
+# Every pair above a threshold, then clusters of a guaranteed radius around real molecules (csrc/neighbors.hip): the number of clusters is
+# a result.
+#
+#   neighbours    the neighbour list of every row: spmm_sim_range twice -- a count pass, a cumsum, an emit pass -- lists ascending, no sort
+#   leaders       Taylor-Butina (order="count") or first-come leaders (order="row") on that list: rounds of spmm_leader_round until no row
+#                 is open, spmm_leader_finish, clusters numbered in the leaders' priority order, spmm_cluster_group for the members
+#   dedup         the rows to keep when near-duplicates are folded into their first occurrence: the leaders under order="row"
+#
+# Ties of the neighbour count go to the LOWER row (RDKit's Butina.ClusterData gives them to the higher index).
+GROUP_MAX_K = 1 << 24       # spmm_cluster_group's limit on the number of clusters
+RANGE_CHUNK = 1 << 18       # columns of one spmm_sim_range launch
+
+
+def _threshold32(threshold) -> float:
+    t = float(np.float32(threshold))
+    if t != t:
+        raise ValueError("the threshold is NaN")
+    return t
+
+
+def _neighbours_tensor(f, t, rows_per_step=2048):
+    """(counts, offsets, nbr) from float64 scores by row blocks.  A float64 product may round (i, j) and (j, i) differently, so the relation
+    is the union of both directions: symmetric, as the kernel's is by construction."""
+    N = f.shape[0]
+    f64 = f.double()
+    keys = []
+    for r0 in range(0, N, rows_per_step):
+        S = f64[r0:r0 + rows_per_step] @ f64.T
+        i, j = torch.nonzero(S >= t, as_tuple=True)
+        i = i + r0
+        off = i != j
+        keys.append(i[off] * N + j[off])
+        keys.append(j[off] * N + i[off])
+    key = torch.unique(torch.cat(keys)) if keys else torch.zeros(0, dtype=torch.int64, device=f.device)      # (sorted: row, then column)
+    counts = torch.bincount(torch.div(key, max(N, 1), rounding_mode="floor"), minlength=N).to(torch.int32)
+    offsets = torch.zeros(N + 1, dtype=torch.int64, device=f.device)
+    offsets[1:] = torch.cumsum(counts.to(torch.int64), 0)
+    return counts, offsets, (key % max(N, 1)).to(torch.int32)
+
+
+def _too_many(M, t, max_pairs):
+    return ValueError(f"{M} neighbour entries at threshold {t!r} exceed max_pairs={max_pairs} (--max_pairs): raise the threshold, or "
+                      f"raise the limit if {4 * M / 2 ** 30:.1f} GiB of list fit in device memory")
+
+
+def _neighbours(f, t, chunk, max_pairs, engine):
+    """-> (counts, offsets, nbr, bad): `bad` is a device flag (the emit pass counted differently from the count pass) not yet read, or None."""
+    N = f.shape[0]
+    if chunk < 1 or max_pairs < 0:
+        raise ValueError(f"neighbours: chunk={chunk} max_pairs={max_pairs}")
+    if not engine:
+        counts, offsets, nbr = _neighbours_tensor(f, t)
+        if nbr.numel() > max_pairs:
+            raise _too_many(nbr.numel(), t, max_pairs)
+        return counts, offsets, nbr, None
+    counts = torch.zeros(N, dtype=torch.int32, device=f.device)
+    for c0 in range(0, N, chunk):
+        ops.sim_range(f, f[c0:c0 + chunk], t, counts, c0=c0)
+    offsets = torch.zeros(N + 1, dtype=torch.int64, device=f.device)
+    offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+    M = int(offsets[-1])                                                      # the one host read: the size of the list
+    if M > max_pairs:
+        raise _too_many(M, t, max_pairs)
+    nbr = torch.empty(M, dtype=torch.int32, device=f.device)
+    again = torch.zeros(N, dtype=torch.int32, device=f.device)
+    for c0 in range(0, N, chunk):
+        ops.sim_range(f, f[c0:c0 + chunk], t, again, c0=c0, offsets=offsets, nbr=nbr)
+    return counts, offsets, nbr, (again != counts).any()
+
+
+@torch.no_grad()
+def neighbours(feats, threshold: float, chunk: int = RANGE_CHUNK, max_pairs: int = 1 << 30, engine: bool = True):
+    """Every row's neighbours above a threshold -> (counts int32 [N], offsets int64 [N + 1], nbr int32 [M]): the neighbours of row i -- the
+    rows j != i with cosine(i, j) >= threshold (rounded to fp32) -- are nbr[offsets[i]:offsets[i + 1]], ascending.  The relation is exactly
+    symmetric, an exact copy of a row is its neighbour, a NaN row has none.  The column side is streamed `chunk` rows at a time (any
+    chunking gives the same bytes).  M, read once between the two passes, is refused above `max_pairs` before the list is allocated."""
+    f = _feats(feats)
+    counts, offsets, nbr, bad = _neighbours(f, _threshold32(threshold), chunk, max_pairs, engine)
+    if bad is not None and bool(bad):
+        raise RuntimeError("neighbours: the emit pass counted other neighbours than the count pass")
+    return counts, offsets, nbr
+
+
+@dataclass
+class LeaderClustering:
+    """The result of `leaders` over N rows: K clusters, each a leader (a real row) and the rows it claimed, every member within the
+    threshold of its leader, no two leaders within it.  Cluster 0 is the first leader in priority order (order="count": the most populated
+    neighbourhood).  The rows of cluster c are members[offsets[c]:offsets[c + 1]], ascending."""
+    leader: torch.Tensor           # int32 [N]: the row's leader (itself for a leader)
+    cluster: torch.Tensor          # int32 [N]
+    leaders: torch.Tensor          # int64 [K]: the leader rows, in cluster order
+    counts: torch.Tensor           # int32 [K]
+    offsets: torch.Tensor          # int64 [K + 1]
+    members: torch.Tensor          # int32 [N]
+    n_neighbours: torch.Tensor     # int32 [N]
+    cosine_to_leader: Optional[torch.Tensor]   # fp32 [N], 1.0 for a leader (None when only a list was given)
+    rounds: int                    # rounds of the parallel rule until no row was open
+    threshold: Optional[float]
+    order: str
+    pairs: int                     # entries of the neighbour list (every pair twice)
+
+
+def _leaders_sequential(counts, offsets, nbr, by_count):
+    """The sequential algorithm in numpy -> (leader int64 [N], rounds): visit the rows in priority order; a row not yet claimed becomes a
+    leader and claims its unclaimed neighbours.  `rounds` is what the parallel rule needs, from the same walk: a leader is decided one
+    round after the last of its higher-priority neighbours, a member one round after the first of its higher-priority leaders."""
+    cnt, off, nb = counts.cpu().numpy().astype(np.int64), offsets.cpu().numpy(), nbr.cpu().numpy().astype(np.int64)
+    N = cnt.shape[0]
+    order = np.lexsort((np.arange(N), -cnt)) if by_count else np.arange(N)
+    rank = np.empty(N, dtype=np.int64)
+    rank[order] = np.arange(N)
+    leader = np.full(N, -1, dtype=np.int64)
+    decided = np.zeros(N, dtype=np.int64)
+    for i in order.tolist():
+        mine = nb[off[i]:off[i + 1]]
+        higher = mine[rank[mine] < rank[i]]
+        if leader[i] < 0:
+            leader[i] = i
+            decided[i] = 1 + (decided[higher].max() if higher.size else 0)
+            free = mine[leader[mine] < 0]
+            leader[free] = i
+        else:
+            led = higher[leader[higher] == higher]
+            decided[i] = 1 + (decided[led].min() if led.size else 0)      # (no such leader: the list was not symmetric)
+    return leader, int(decided.max()) if N else 0
+
+
+def _run_rounds(counts, offsets, nbr, by_count, sync_every, bad):
+    """Rounds of spmm_leader_round until one leaves no row open -> (state, rounds).  The open counts are read every `sync_every` rounds;
+    a round past the last one copies the state, so neither depends on sync_every.  `bad` (neighbours' device flag) rides on the first read."""
+    N, dev = counts.numel(), counts.device
+    state, other = torch.zeros(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev)
+    rounds = 0
+    while True:
+        opened = torch.zeros(sync_every + 1, dtype=torch.int32, device=dev)
+        for r in range(sync_every):
+            ops.leader_round(counts, offsets, nbr, state, other, opened[r:r + 1], by_count=by_count)
+            state, other = other, state
+        if bad is not None:
+            opened[sync_every] = bad.to(torch.int32)
+        host = opened.tolist()                                               # the one host read of these rounds
+        if bad is not None and host[sync_every]:
+            raise RuntimeError("neighbours: the emit pass counted other neighbours than the count pass")
+        bad = None
+        for r in range(sync_every):
+            if host[r] == 0:
+                return state, rounds + r + 1
+        rounds += sync_every
+
+
+@torch.no_grad()
+def leaders(feats_or_csr, threshold: Optional[float] = None, order: str = "count", sync_every: int = 4, chunk: int = RANGE_CHUNK,
+            max_pairs: int = 1 << 30, engine: bool = True) -> LeaderClustering:
+    """Threshold clustering of the rows: Taylor-Butina (order="count": the row with the most neighbours leads first, equal counts to the
+    lower row) or first-come leaders (order="row").  feats_or_csr: a MoleculeIndex / [N, E] features with a `threshold`, or a symmetric
+    neighbour list (counts, offsets, nbr) as `neighbours` returns it.  The parallel rule of spmm_leader_round gives the sequential
+    algorithm's result; its worst case is one round per row (a path under order="row"), a similarity graph takes a handful."""
+    if order not in ("count", "row"):
+        raise ValueError(f"leaders: order={order!r}: 'count' or 'row'")
+    if sync_every < 1:
+        raise ValueError(f"leaders: sync_every={sync_every}")
+    by_count = order == "count"
+    f, bad, t = None, None, None
+    if isinstance(feats_or_csr, (tuple, list)):
+        n_nb, offsets, nbr = feats_or_csr
+        n_nb, offsets, nbr = n_nb.to(torch.int32).contiguous(), offsets.to(torch.int64).contiguous(), nbr.to(torch.int32).contiguous()
+    else:
+        if threshold is None:
+            raise ValueError("leaders: features need a threshold")
+        f, t = _feats(feats_or_csr), _threshold32(threshold)
+        n_nb, offsets, nbr, bad = _neighbours(f, t, chunk, max_pairs, engine)
+    N, dev = n_nb.numel(), n_nb.device
+    if engine:
+        if N:
+            state, rounds = _run_rounds(n_nb, offsets, nbr, by_count, sync_every, bad)
+        else:
+            state, rounds = torch.zeros(0, dtype=torch.int32, device=dev), 0
+        leader = torch.empty(N, dtype=torch.int32, device=dev)
+        ops.leader_finish(n_nb, offsets, nbr, state, leader, by_count=by_count)
+    else:
+        lead, rounds = _leaders_sequential(n_nb, offsets, nbr, by_count)
+        leader = torch.from_numpy(lead).to(dev).to(torch.int32)
+    ar = torch.arange(N, device=dev)
+    rows = torch.nonzero(leader.to(torch.int64) == ar).flatten()
+    if by_count:                                                              # a sort over the leaders only: more neighbours first, then the lower row
+        rows = rows[torch.sort(rows - n_nb[rows].to(torch.int64) * N).indices]
+    K = rows.numel()
+    if K > GROUP_MAX_K:
+        raise ValueError(f"leaders: {K} clusters exceed spmm_cluster_group's limit of 2^24 = {GROUP_MAX_K}: lower the threshold")
+    number = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    number[rows] = torch.arange(K, dtype=torch.int32, device=dev)
+    lead64 = leader.to(torch.int64)
+    cluster = torch.where(lead64 >= 0, number[lead64.clamp_min(0)], torch.full_like(number, -1)) if N else number
+    if engine and K:
+        counts = torch.empty(K, dtype=torch.int32, device=dev)
+        offs = torch.empty(K + 1, dtype=torch.int64, device=dev)
+        members = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        ops.cluster_group(cluster, K, counts, offs, members, torch.empty(1, dtype=torch.int32, device=dev))
+    else:
+        counts, offs, members = _group_tensor(cluster, K)
+    cos = None
+    if f is not None:
+        cos = (f * f.index_select(0, lead64.clamp_min(0))).sum(1)
+        cos = torch.where(lead64 == ar, torch.ones_like(cos), cos)
+    return LeaderClustering(leader=leader, cluster=cluster, leaders=rows, counts=counts, offsets=offs, members=members, n_neighbours=n_nb,
+                            cosine_to_leader=cos, rounds=rounds, threshold=t, order=order, pairs=int(nbr.numel()))
+
+
+@torch.no_grad()
+def dedup(feats, threshold: float, engine: bool = True, max_pairs: int = 1 << 30) -> torch.Tensor:
+    """keep bool [N]: False for a row within `threshold` of an earlier kept row -- the leaders under order="row", so the first occurrence of
+    every set of near-duplicates stays and `leaders(..., order="row").leader` names the row each dropped one was folded into."""
+    res = leaders(feats, threshold, order="row", engine=engine, max_pairs=max_pairs)
+    return res.leader.to(torch.int64) == torch.arange(res.leader.numel(), device=res.leader.device)

@@ -579,6 +579,58 @@ def cluster_centroids(f, best, counts, offsets, members, centres, norm, medoid, 
     return centres, norm, medoid
 
 
+def sim_range(f, c, threshold, counts, *, r0=0, c0=0, offsets=None, nbr=None):
+    """Neighbours above a threshold (csrc/neighbors.hip): rows f [n, E] = library indices r0 .. against one chunk c [nc, E] = indices c0 .. of
+    the column side.  counts int32 [n] += every row's hits (score >= threshold, the diagonal r0 + i == c0 + j excluded).  With offsets int64
+    [>= n] and nbr int32 [M] the hits are also written, ascending, to nbr[offsets[i] + counts[i] ...] (never at or past M)."""
+    n, E = f.shape
+    nc = c.shape[0]
+    assert f.dtype == torch.float32 and c.dtype == torch.float32 and (nc == 0 or c.shape[1] == E)
+    assert counts.dtype == torch.int32 and counts.numel() == n and counts.is_contiguous()
+    assert (offsets is None) == (nbr is None)
+    assert nbr is None or (offsets.dtype == torch.int64 and offsets.numel() >= n and offsets.is_contiguous() and nbr.dtype == torch.int32
+                           and nbr.is_contiguous())
+    _call("spmm_sim_range", _p(f) if n > 0 else None, _row_stride(f) if n > 0 else E, int(r0), n, _p(c) if nc > 0 else None,
+          _row_stride(c) if nc > 0 else E, int(c0), nc, E, float(threshold), _p(counts) if n > 0 else None, _p(offsets),
+          _p(nbr) if nbr is None or nbr.numel() else _p(offsets),      # (an empty list has no storage: nbr_len = 0 keeps the stand-in unwritten)
+          0 if nbr is None else nbr.numel(), _st())
+    return counts
+
+
+def _csr(counts, offsets, nbr, n, by_count):
+    assert offsets.dtype == torch.int64 and offsets.numel() == n + 1 and offsets.is_contiguous()
+    assert nbr.dtype == torch.int32 and nbr.is_contiguous()
+    assert counts is None or (counts.dtype == torch.int32 and counts.numel() == n and counts.is_contiguous())
+    assert counts is not None or not by_count
+    # (an empty list has no storage: any valid pointer stands in for it, nbr_len = 0 keeps it from being read)
+    return _p(counts) if by_count else None, _p(offsets), _p(nbr) if nbr.numel() else _p(offsets), nbr.numel()
+
+
+def leader_round(counts, offsets, nbr, state_in, state_out, open_out, *, by_count=True):
+    """One round of the leader rule on a symmetric neighbour list (csrc/neighbors.hip): state int32 [n] 0 open / 1 leader / 2 member, read
+    from state_in, written to state_out; open_out int32 [1] += the rows still open."""
+    n = state_in.numel()
+    assert state_in.dtype == state_out.dtype == torch.int32 and state_out.numel() == n and state_in.is_contiguous() and state_out.is_contiguous()
+    assert state_in.data_ptr() != state_out.data_ptr() or n == 0
+    assert open_out.dtype == torch.int32 and open_out.numel() == 1
+    if n == 0:
+        return state_out
+    pc, po, pn, m = _csr(counts, offsets, nbr, n, by_count)
+    _call("spmm_leader_round", pc, po, pn, m, n, int(bool(by_count)), _p(state_in), _p(state_out), _p(open_out), _st())
+    return state_out
+
+
+def leader_finish(counts, offsets, nbr, state, leader, *, by_count=True):
+    """leader int32 [n] = the row itself for a leader, else the highest-priority leader among its neighbours (-1: none)."""
+    n = state.numel()
+    assert state.dtype == torch.int32 and leader.dtype == torch.int32 and leader.numel() == n and state.is_contiguous() and leader.is_contiguous()
+    if n == 0:
+        return leader
+    pc, po, pn, m = _csr(counts, offsets, nbr, n, by_count)
+    _call("spmm_leader_finish", pc, po, pn, m, n, int(bool(by_count)), _p(state), _p(leader), _st())
+    return leader
+
+
 def enqueue(feats, queue, w3, qT, ptr, *, Bloc, advance=True, skip_flag=None):
     n, E = feats.shape
     _call("spmm_enqueue", _p(feats), n, E, _p(queue), queue.shape[1], _p(w3), _p(qT), _row_stride(qT), Bloc, _p(ptr),
