@@ -39,7 +39,8 @@ def _feats(index_or_feats) -> torch.Tensor:
 
 
 def _score_key(best: torch.Tensor) -> torch.Tensor:
-    """spmm_sim_topk's order of scores as an int64 key: larger score <-> larger key, -0 = +0, NaN -> 0 (below -inf's image)."""
+    """The host mirror of csrc/sim_scan.h's score_key, which defines the order: larger score <-> larger int64 key, -0 = +0, NaN -> 0
+    (below -inf's image)."""
     b = best.to(torch.float32) + 0.0
     u = b.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
     key = torch.where(u >= 0x80000000, 0xFFFFFFFF - u, u | 0x80000000)
@@ -76,6 +77,18 @@ def _merge_tensor(best, idx, nb, ni):
     ka, kb = _score_key(best), _score_key(nb)
     take = (ni >= 0) & ((idx < 0) | (kb > ka) | ((kb == ka) & (ni < idx)))
     return torch.where(take, nb, best), torch.where(take, ni, idx)
+
+
+def _group(idx, K, engine):
+    """(counts int32 [K], offsets int64 [K + 1], members int32 [n], -1 past offsets[K]): spmm_cluster_group, or its tensor form."""
+    if not (engine and K):
+        return _group_tensor(idx, K)
+    n, dev = idx.numel(), idx.device
+    counts = torch.empty(K, dtype=torch.int32, device=dev)
+    offsets = torch.empty(K + 1, dtype=torch.int64, device=dev)
+    members = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    ops.cluster_group(idx, K, counts, offsets, members, torch.empty(1, dtype=torch.int32, device=dev))
+    return counts, offsets, members
 
 
 def _group_tensor(idx, K):
@@ -204,15 +217,11 @@ def _reseed(f, best, bad, centres):
 
 def _iteration(f, centres, prev, chunk, engine):
     """assign -> group -> centroids -> re-seed, all enqueued: -> dict of device tensors (nothing read on the host)."""
-    N, E = f.shape
     K, dev = centres.shape[0], f.device
     if engine:
         changed = torch.zeros(1, dtype=torch.int32, device=dev)
         best, idx = assign(f, centres, chunk=chunk, prev=prev, changed=changed)
-        counts = torch.empty(K, dtype=torch.int32, device=dev)
-        offsets = torch.empty(K + 1, dtype=torch.int64, device=dev)
-        members = torch.full((N,), -1, dtype=torch.int32, device=dev)
-        ops.cluster_group(idx, K, counts, offsets, members, torch.empty(1, dtype=torch.int32, device=dev))
+        counts, offsets, members = _group(idx, K, engine)
         new = centres.clone()
         norm = torch.empty(K, dtype=torch.float32, device=dev)
         medoid = torch.empty(K, dtype=torch.int32, device=dev)
@@ -220,7 +229,7 @@ def _iteration(f, centres, prev, chunk, engine):
     else:
         best, idx = _assign_tensor(f, centres)
         changed = (idx != prev).sum().to(torch.int32).view(1)
-        counts, offsets, members = _group_tensor(idx, K)
+        counts, offsets, members = _group(idx, K, engine)
         new, norm, medoid = _centroids_tensor(f, best, idx, counts, offsets, members, centres)
     bad = (counts == 0) | ~(norm >= NORM_GUARD)
     new = _reseed(f, best, bad, new)
@@ -345,6 +354,12 @@ def _neighbours(f, t, chunk, max_pairs, engine):
     return counts, offsets, nbr, (again != counts).any()
 
 
+def _refuse_emit_mismatch(bad):
+    """`bad`: _neighbours' flag once it has been read on the host."""
+    if bad:
+        raise RuntimeError("neighbours: the emit pass counted other neighbours than the count pass")
+
+
 @torch.no_grad()
 def neighbours(feats, threshold: float, chunk: int = RANGE_CHUNK, max_pairs: int = 1 << 30, engine: bool = True):
     """Every row's neighbours above a threshold -> (counts int32 [N], offsets int64 [N + 1], nbr int32 [M]): the neighbours of row i -- the
@@ -353,8 +368,7 @@ def neighbours(feats, threshold: float, chunk: int = RANGE_CHUNK, max_pairs: int
     chunking gives the same bytes).  M, read once between the two passes, is refused above `max_pairs` before the list is allocated."""
     f = _feats(feats)
     counts, offsets, nbr, bad = _neighbours(f, _threshold32(threshold), chunk, max_pairs, engine)
-    if bad is not None and bool(bad):
-        raise RuntimeError("neighbours: the emit pass counted other neighbours than the count pass")
+    _refuse_emit_mismatch(bad is not None and bool(bad))
     return counts, offsets, nbr
 
 
@@ -416,8 +430,7 @@ def _run_rounds(counts, offsets, nbr, by_count, sync_every, bad):
         if bad is not None:
             opened[sync_every] = bad.to(torch.int32)
         host = opened.tolist()                                               # the one host read of these rounds
-        if bad is not None and host[sync_every]:
-            raise RuntimeError("neighbours: the emit pass counted other neighbours than the count pass")
+        _refuse_emit_mismatch(host[sync_every])                              # (0 when no flag rode along)
         bad = None
         for r in range(sync_every):
             if host[r] == 0:
@@ -468,13 +481,7 @@ def leaders(feats_or_csr, threshold: Optional[float] = None, order: str = "count
     number[rows] = torch.arange(K, dtype=torch.int32, device=dev)
     lead64 = leader.to(torch.int64)
     cluster = torch.where(lead64 >= 0, number[lead64.clamp_min(0)], torch.full_like(number, -1)) if N else number
-    if engine and K:
-        counts = torch.empty(K, dtype=torch.int32, device=dev)
-        offs = torch.empty(K + 1, dtype=torch.int64, device=dev)
-        members = torch.full((N,), -1, dtype=torch.int32, device=dev)
-        ops.cluster_group(cluster, K, counts, offs, members, torch.empty(1, dtype=torch.int32, device=dev))
-    else:
-        counts, offs, members = _group_tensor(cluster, K)
+    counts, offs, members = _group(cluster, K, engine)
     cos = None
     if f is not None:
         cos = (f * f.index_select(0, lead64.clamp_min(0))).sum(1)

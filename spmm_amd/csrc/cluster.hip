@@ -1,19 +1,11 @@
 // Library clustering: nearest centre of every row (spmm_centroid_assign), members of every cluster (spmm_cluster_group) and the clusters'
 // centres, norms and medoids (spmm_cluster_centroids); include/spmm_hip.h.
 //
-// centroid_assign.  The arithmetic of retrieval (csrc/retrieve.hip) with the roles swapped: many rows, few centres.  A workgroup owns
-// AR = 128 rows -- each of its four waves two MFMA blocks of 16 -- and keeps them in REGISTERS for the whole launch (2 x E / 4 per lane); the
-// centres go through LDS once per workgroup in tiles of 32 (E = 512: 16), the next tile's global loads in flight under the current tile's MFMAs.
-// The 16 x 16 scores of (centre block, row block) never leave the accumulators: D's column (lane & 15) is the row, its rows 4 g + r the
-// centres, so every lane folds its four scores into a running best of its own -- one 64-bit key per row block -- and the four lane groups
-// of a row are combined once, after the last tile.  No score tile, no per-row list, no workspace.
-//
-// Same bits as spmm_sim_topk(q = rows, f = centres, k = 1).  The score of (row, centre) is one accumulator's chain of
-// v_mfma_f32_16x16x4_f32: lane (c, g) feeds elements 16 kb + 4 g .. + 3 of its centre (A, from LDS) and of its row (B, registers), component
-// m to the m-th of four MFMAs -- kb ascending, then m, then the k slot g, retrieve.hip's order; a product does not know which factor was A.
-// Candidates are (score, centre index) under that kernel's total order (larger score, then lower index; NaN below every number; -0 = +0;
-// an empty state below everything), as one integer key: the best of a set does not depend on how the set was cut into lanes, tiles or
-// chunks.
+// centroid_assign.  The arithmetic of retrieval (csrc/retrieve.hip) with the roles swapped: many rows, few centres -- the row-stationary
+// scan of csrc/sim_scan.h with the centres as its column side.  A tile's scores never leave the accumulators: every lane folds its four
+// scores of a (centre block, row block) into a running best of its own -- one 64-bit key per row block -- and the four lane groups of a
+// row are combined once, after the last tile.  No score tile, no per-row list, no workspace.  The chain and the candidate order are that
+// header's, so the result has the bits of spmm_sim_topk(q = rows, f = centres, k = 1), however the centre list is cut into chunks.
 //
 // cluster_group.  A stable counting sort of the rows by cluster.  The rows are cut into nb blocks; launch 1 counts every block's rows per
 // cluster (integer atomics into the block's own line of the [nb, K] table), launch 2 turns each column into running starts and the column
@@ -24,99 +16,40 @@
 // member order (a sequential fp32 chain per component) and finds its medoid candidate; a second launch, one workgroup per cluster, adds the
 // piece sums in ascending order, takes the norm on a fixed tree and writes the centre.  The order is a function of the member list alone.
 // No floating-point atomics.
-#include "common.h"
+#include "sim_scan.h"
 #include "../../include/spmm_hip.h"
 
 namespace {
 
+using namespace sim_scan;
+
 constexpr int NT = 256;
-constexpr int AR = 128;          // rows of an assign workgroup: 4 waves x NB blocks of 16
-constexpr int NB = 2;            // row blocks of a wave
 constexpr int PIECE = 256;       // members of one partial centroid sum
 constexpr long GROUP_TABLE = 1L << 24;      // entries of cluster_group's [nb, K] table at the most
 
-// Monotonic image of a score (retrieve.hip): larger float <-> larger key; -0 = +0; NaN -> 0, below -inf's image.
-__device__ __forceinline__ uint32_t score_key(float s) {
-  if (s != s) return 0u;
-  if (s == 0.0f) s = 0.0f;
-  const uint32_t u = __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_score(uint32_t k) {
-  if (k == 0u) return __uint_as_float(0x7fc00000u);
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-// candidate (score, centre index < 2^31) as one key: a larger key is a better candidate, 0 is the empty slot
-__device__ __forceinline__ uint64_t cand_key(float s, uint32_t idx) { return ((uint64_t)score_key(s) << 32) | (0xffffffffu - idx); }
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
-  const uint32_t lo = __shfl_xor((uint32_t)v, m, 64), hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-
 // ------------------------------------------------------------------------------------------------------------------ assign
 template <int E64>
-__global__ __launch_bounds__(NT) void centroid_assign(const float* __restrict__ f, long ldf, const float* __restrict__ cen, long ldc, int c0,
-                                                      int n, int Kc, int merge, float* __restrict__ best, int* __restrict__ assign,
-                                                      const int* __restrict__ prev, int* __restrict__ changed) {
-  constexpr int E = 64 * E64, EP = E + 4, KB = E / 16;
-  constexpr int CB = E64 < 8 ? 2 : 1, CT = 16 * CB;                        // centre blocks of an LDS tile (E = 512: one, the tile stays under 64 KiB)
-  constexpr int LD4 = CT * (E / 4) / NT;                                   // 16-byte loads of a thread per centre tile
-  __shared__ __attribute__((aligned(16))) float cl[CT * EP];
+__global__ __launch_bounds__(Shape<E64>::NT) void centroid_assign(const float* __restrict__ f, long ldf, const float* __restrict__ cen, long ldc,
+                                                                  int c0, int n, int Kc, int merge, float* __restrict__ best,
+                                                                  int* __restrict__ assign, const int* __restrict__ prev,
+                                                                  int* __restrict__ changed) {
+  using S = Shape<E64>;
+  constexpr int AR = S::AR, NB = S::NB, CB = S::CB, CT = S::CT;
+  __shared__ __attribute__((aligned(16))) float cl[CT * S::EP];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
   const long row0 = (long)blockIdx.x * AR + w * (NB * 16);
-  f32x4 rows[NB][KB];
+  f32x4 rows[NB][S::KB];
 #pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const long row = min(row0 + b * 16 + c, (long)n - 1);                   // rows past the end: a valid address, never written back
-    const float* fp = f + row * ldf + g * 4;
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) rows[b][kb] = *reinterpret_cast<const f32x4*>(fp + kb * 16);
-  }
+  for (int b = 0; b < NB; ++b) load_row_block<E64>(f, ldf, row0 + b * 16 + c, n, g, rows[b]);
   uint64_t mine[NB];
 #pragma unroll
-  for (int b = 0; b < NB; ++b) mine[b] = 0;
-  f32x4 pre[LD4];
-  auto fetch = [&](int t) {
-#pragma unroll
-    for (int i = 0; i < LD4; ++i) {
-      const int e = tid + i * NT, r = e / (E / 4), e4 = e % (E / 4);
-      const int j = min(t * CT + r, Kc - 1);                                // centres past the chunk: a valid address, dropped below
-      pre[i] = *reinterpret_cast<const f32x4*>(cen + (long)j * ldc + e4 * 4);
-    }
-  };
-  auto stage = [&]() {
-#pragma unroll
-    for (int i = 0; i < LD4; ++i) {
-      const int e = tid + i * NT, r = e / (E / 4), e4 = e % (E / 4);
-      *reinterpret_cast<f32x4*>(cl + r * EP + e4 * 4) = pre[i];
-    }
-  };
-  const int tiles = (Kc + CT - 1) / CT;
-  fetch(0);
-  stage();
-  __syncthreads();
-  for (int t = 0; t < tiles; ++t) {
-    if (t + 1 < tiles) fetch(t + 1);
+  for (int b = 0; b < NB; ++b) mine[b] = EMPTY_KEY;
+  RowScan<E64> scan(cen, ldc, Kc, cl);
+  for (int t = 0; t < scan.tiles; ++t) {
     f32x4 acc[CB][NB];
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-      for (int b = 0; b < NB; ++b) acc[cb][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* ap = cl + c * EP + g * 4;
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      f32x4 a[CB];
-#pragma unroll
-      for (int cb = 0; cb < CB; ++cb) a[cb] = *reinterpret_cast<const f32x4*>(ap + cb * 16 * EP + kb * 16);
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-          for (int b = 0; b < NB; ++b) acc[cb][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cb][m], rows[b][kb][m], acc[cb][b], 0, 0, 0);
-    }
-    // D: column (lane & 15) = row of the block, row 4 g + r = centre of the block; the key carries the index, so `>` keeps the lowest of equals
+    scan.scores(t, rows, acc);
+    // the key carries the index, so `>` keeps the lowest of equals; centres past the chunk are dropped
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
@@ -130,11 +63,7 @@ __global__ __launch_bounds__(NT) void centroid_assign(const float* __restrict__ 
           }
         }
       }
-    __syncthreads();
-    if (t + 1 < tiles) {
-      stage();
-      __syncthreads();
-    }
+    scan.next(t);
   }
   int diff = 0;
 #pragma unroll
@@ -153,8 +82,8 @@ __global__ __launch_bounds__(NT) void centroid_assign(const float* __restrict__ 
           m = s > m ? s : m;
         }
       }
-      const int ia = m == 0 ? -1 : (int)(0xffffffffu - (uint32_t)m);
-      best[row] = m == 0 ? -__builtin_huge_valf() : key_score((uint32_t)(m >> 32));
+      const int ia = m == EMPTY_KEY ? -1 : (int)key_index(m);
+      best[row] = m == EMPTY_KEY ? -__builtin_huge_valf() : key_score(key_image(m));
       assign[row] = ia;
       if (prev != nullptr && prev[row] != ia) ++diff;
     }
@@ -334,44 +263,26 @@ inline int group_blocks(long n, int K) {
 inline long pieces_max(long n, int K) { return n / PIECE + K; }            // sum over clusters of ceil(count / PIECE), at the most
 inline long align16(long b) { return (b + 15) & ~15L; }
 
-template <int E64>
-void launch_assign(const float* f, long ldf, const float* c, long ldc, int c0, long n, int Kc, int merge, float* best, int* assign,
-                   const int* prev, int* changed, hipStream_t stream) {
-  hipLaunchKernelGGL(centroid_assign<E64>, dim3((unsigned)((n + AR - 1) / AR)), dim3(NT), 0, stream, f, ldf, c, ldc, c0, (int)n, Kc, merge, best,
-                     assign, prev, changed);
-}
-
 }  // namespace
 
 extern "C" int spmm_centroid_assign(const float* f, long ldf, const float* c, long ldc, long c0, long n, int Kc, int E, float* best, int* assign,
                                     int merge, const int* prev, int* changed, spmm_stream_t stream) {
-  SPMM_CHECK_SHAPE(E >= 64 && E <= 512 && E % 64 == 0, "spmm_centroid_assign: E=%d must be a multiple of 64 up to 512", E);
+  if (int e = check_width("spmm_centroid_assign", E)) return e;
   SPMM_CHECK_SHAPE(Kc >= 1, "spmm_centroid_assign: Kc=%d must be at least 1", Kc);
   SPMM_CHECK_SHAPE(c0 >= 0 && c0 + Kc <= 0x7fffffffL, "spmm_centroid_assign: c0=%ld with Kc=%d must keep centre indices in [0, 2^31 - 1)", c0, Kc);
-  SPMM_CHECK_SHAPE(n >= 0 && n <= 0x7fffff00L, "spmm_centroid_assign: n=%ld must be in [0, 2^31 - 256] rows", n);
+  if (int e = check_rows("spmm_centroid_assign", n)) return e;
   SPMM_CHECK_SHAPE(merge == 0 || merge == 1, "spmm_centroid_assign: merge=%d must be 0 or 1", merge);
   SPMM_CHECK_SHAPE((prev == nullptr) == (changed == nullptr), "spmm_centroid_assign: prev and changed come together");
-  SPMM_CHECK_SHAPE((reinterpret_cast<uintptr_t>(prev) & 3) == 0 && (reinterpret_cast<uintptr_t>(changed) & 3) == 0,
-                   "spmm_centroid_assign: misaligned prev / changed (4 bytes)");
+  SPMM_CHECK_SHAPE(aligned(prev, 4) && aligned(changed, 4), "spmm_centroid_assign: misaligned prev / changed (4 bytes)");
   if (n == 0) return SPMM_OK;
   SPMM_CHECK_SHAPE(best && assign, "spmm_centroid_assign: null best / assign (the state)");
-  SPMM_CHECK_SHAPE((reinterpret_cast<uintptr_t>(best) & 3) == 0 && (reinterpret_cast<uintptr_t>(assign) & 3) == 0,
-                   "spmm_centroid_assign: misaligned best / assign (4 bytes)");
-  SPMM_CHECK_SHAPE(f && c, "spmm_centroid_assign: null f / c");
-  SPMM_CHECK_SHAPE((reinterpret_cast<uintptr_t>(f) & 15) == 0 && (reinterpret_cast<uintptr_t>(c) & 15) == 0,
-                   "spmm_centroid_assign: f / c must be 16-byte aligned");
-  SPMM_CHECK_SHAPE(ldf >= E && ldf % 4 == 0 && ldc >= E && ldc % 4 == 0,
-                   "spmm_centroid_assign: ldf=%ld ldc=%ld must be multiples of 4, at least E=%d", ldf, ldc, E);
-  switch (E / 64) {
-    case 1: launch_assign<1>(f, ldf, c, ldc, (int)c0, n, Kc, merge, best, assign, prev, changed, stream); break;
-    case 2: launch_assign<2>(f, ldf, c, ldc, (int)c0, n, Kc, merge, best, assign, prev, changed, stream); break;
-    case 3: launch_assign<3>(f, ldf, c, ldc, (int)c0, n, Kc, merge, best, assign, prev, changed, stream); break;
-    case 4: launch_assign<4>(f, ldf, c, ldc, (int)c0, n, Kc, merge, best, assign, prev, changed, stream); break;
-    case 5: launch_assign<5>(f, ldf, c, ldc, (int)c0, n, Kc, merge, best, assign, prev, changed, stream); break;
-    case 6: launch_assign<6>(f, ldf, c, ldc, (int)c0, n, Kc, merge, best, assign, prev, changed, stream); break;
-    case 7: launch_assign<7>(f, ldf, c, ldc, (int)c0, n, Kc, merge, best, assign, prev, changed, stream); break;
-    default: launch_assign<8>(f, ldf, c, ldc, (int)c0, n, Kc, merge, best, assign, prev, changed, stream); break;
-  }
+  SPMM_CHECK_SHAPE(aligned(best, 4) && aligned(assign, 4), "spmm_centroid_assign: misaligned best / assign (4 bytes)");
+  if (int e = check_operands("spmm_centroid_assign", f, ldf, c, ldc, E)) return e;
+  dispatch_width(E, [&](auto e64) {
+    constexpr int E64 = decltype(e64)::value, AR = Shape<E64>::AR;
+    hipLaunchKernelGGL(centroid_assign<E64>, dim3((unsigned)((n + AR - 1) / AR)), dim3(Shape<E64>::NT), 0, stream, f, ldf, c, ldc, (int)c0, (int)n,
+                       Kc, merge, best, assign, prev, changed);
+  });
   SPMM_LAUNCH_CHECK("spmm_centroid_assign");
   return SPMM_OK;
 }
@@ -386,15 +297,13 @@ extern "C" int spmm_cluster_group(const int* assign, long n, int K, int* counts,
   SPMM_CHECK_SHAPE(K >= 1 && K <= GROUP_TABLE, "spmm_cluster_group: K=%d must be in [1, 2^24]", K);
   SPMM_CHECK_SHAPE(n >= 0 && n <= 0x7fffff00L, "spmm_cluster_group: n=%ld must be in [0, 2^31 - 256] rows", n);
   SPMM_CHECK_SHAPE(counts && offsets && outside, "spmm_cluster_group: null counts / offsets / outside");
-  SPMM_CHECK_SHAPE((reinterpret_cast<uintptr_t>(counts) & 3) == 0 && (reinterpret_cast<uintptr_t>(offsets) & 7) == 0 &&
-                       (reinterpret_cast<uintptr_t>(outside) & 3) == 0,
+  SPMM_CHECK_SHAPE(aligned(counts, 4) && aligned(offsets, 8) && aligned(outside, 4),
                    "spmm_cluster_group: misaligned counts / offsets / outside (4 / 8 / 4 bytes)");
   SPMM_CHECK_SHAPE(n == 0 || (assign && members), "spmm_cluster_group: null assign / members");
-  SPMM_CHECK_SHAPE((reinterpret_cast<uintptr_t>(assign) & 3) == 0 && (reinterpret_cast<uintptr_t>(members) & 3) == 0,
-                   "spmm_cluster_group: misaligned assign / members (4 bytes)");
+  SPMM_CHECK_SHAPE(aligned(assign, 4) && aligned(members, 4), "spmm_cluster_group: misaligned assign / members (4 bytes)");
   const int nb = group_blocks(n, K);
   const long need = align16((long)nb * K * 4);
-  SPMM_CHECK_SHAPE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && workspace_bytes >= need,
+  SPMM_CHECK_SHAPE(workspace && aligned(workspace, 16) && workspace_bytes >= need,
                    "spmm_cluster_group: workspace of %ld bytes (16-byte aligned) needed, %ld given (spmm_cluster_group_workspace_bytes)", need,
                    workspace ? workspace_bytes : 0L);
   int* table = reinterpret_cast<int*>(workspace);
@@ -435,14 +344,12 @@ extern "C" int spmm_cluster_centroids(const float* f, long ldf, long n, int E, c
   SPMM_CHECK_SHAPE(counts && offsets && centres && norm && medoid, "spmm_cluster_centroids: null counts / offsets / centres / norm / medoid");
   SPMM_CHECK_SHAPE(n == 0 || (f && best && members), "spmm_cluster_centroids: null f / best / members");
   SPMM_CHECK_SHAPE(ldc >= E && (n == 0 || ldf >= E), "spmm_cluster_centroids: ldf=%ld ldc=%ld must be at least E=%d", ldf, ldc, E);
-  SPMM_CHECK_SHAPE((reinterpret_cast<uintptr_t>(f) & 3) == 0 && (reinterpret_cast<uintptr_t>(best) & 3) == 0 &&
-                       (reinterpret_cast<uintptr_t>(counts) & 3) == 0 && (reinterpret_cast<uintptr_t>(offsets) & 7) == 0 &&
-                       (reinterpret_cast<uintptr_t>(members) & 3) == 0 && (reinterpret_cast<uintptr_t>(centres) & 3) == 0 &&
-                       (reinterpret_cast<uintptr_t>(norm) & 3) == 0 && (reinterpret_cast<uintptr_t>(medoid) & 3) == 0,
+  SPMM_CHECK_SHAPE(aligned(f, 4) && aligned(best, 4) && aligned(counts, 4) && aligned(offsets, 8) && aligned(members, 4) && aligned(centres, 4) &&
+                       aligned(norm, 4) && aligned(medoid, 4),
                    "spmm_cluster_centroids: misaligned pointer (offsets 8 bytes, the others 4)");
   const long p = pieces_max(n, K);
   const long need = align16(((long)K + 1) * 8) + align16(p * 8) + align16(p * E * 4);
-  SPMM_CHECK_SHAPE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && workspace_bytes >= need,
+  SPMM_CHECK_SHAPE(workspace && aligned(workspace, 16) && workspace_bytes >= need,
                    "spmm_cluster_centroids: workspace of %ld bytes (16-byte aligned) needed, %ld given (spmm_cluster_centroids_workspace_bytes)",
                    need, workspace ? workspace_bytes : 0L);
   char* ws = reinterpret_cast<char*>(workspace);

@@ -1,12 +1,8 @@
 // Threshold clustering: every row's neighbours above a similarity threshold (spmm_sim_range) and the leaders of a neighbour list -- Taylor-
 // Butina / first-come sphere exclusion (spmm_leader_round, spmm_leader_finish); include/spmm_hip.h.
 //
-// sim_range.  csrc/cluster.hip's centroid_assign with the library on both sides: a workgroup owns AR = 128 rows -- each of its four waves
-// two MFMA blocks of 16 -- and keeps them in REGISTERS for the whole launch; the column side goes through LDS once per workgroup in tiles
-// of 32 (E = 512: 16), the next tile's global loads in flight under the current tile's MFMAs.  The 16 x 16 scores of (column block, row
-// block) never leave the accumulators: D's column (lane & 15) is the row, its rows 4 g + r the columns.  The score of a pair is that
-// kernel's accumulator chain (kb ascending, then component m, then the k slot g), so it has spmm_sim_topk's bits, and score(i, j) has
-// score(j, i)'s: a product does not know which factor was A.
+// sim_range.  csrc/cluster.hip's centroid_assign with the library on both sides: the row-stationary scan of csrc/sim_scan.h, whose chain
+// gives a pair spmm_sim_topk's bits and score(i, j) score(j, i)'s.
 //
 // Ordered emission without atomics or a sort.  A row of a wave's block lives in the four lanes (c, g = 0 .. 3); nobody else writes its
 // list.  Within a tile the column index ascends with (column block cb, lane group g, accumulator row r), so a lane's hits of one (cb, row
@@ -18,83 +14,43 @@
 // leader_round / leader_finish.  One wave64 per row, its lanes striding the row's list (a row with 10^5 neighbours is 1 600 steps of a
 // wave, not one thread's loop).  A round reads state_in only and writes state_out only; the open rows are counted with one integer atomic
 // per wave.  No floating-point atomics anywhere.
-#include "common.h"
+#include "sim_scan.h"
 #include "../../include/spmm_hip.h"
 
 namespace {
 
+using namespace sim_scan;
+
 constexpr int NT = 256;
-constexpr int AR = 128;          // rows of a workgroup: 4 waves x NB blocks of 16
-constexpr int NB = 2;            // row blocks of a wave
 constexpr int WR = 4;            // rows (waves) of a leader workgroup
 
 // ------------------------------------------------------------------------------------------------------------------ sim_range
 template <int E64, bool EMIT>
-__global__ __launch_bounds__(NT) void sim_range(const float* __restrict__ f, long ldf, int r0, int n, const float* __restrict__ col, long ldc,
-                                                int c0, int nc, float threshold, int* __restrict__ counts, const long* __restrict__ offsets,
-                                                int* __restrict__ nbr, long nbr_len) {
-  constexpr int E = 64 * E64, EP = E + 4, KB = E / 16;
-  constexpr int CB = E64 < 8 ? 2 : 1, CT = 16 * CB;                        // column blocks of an LDS tile (E = 512: one, the tile stays under 64 KiB)
-  constexpr int LD4 = CT * (E / 4) / NT;                                   // 16-byte loads of a thread per column tile
-  __shared__ __attribute__((aligned(16))) float cl[CT * EP];
+__global__ __launch_bounds__(Shape<E64>::NT) void sim_range(const float* __restrict__ f, long ldf, int r0, int n, const float* __restrict__ col,
+                                                            long ldc, int c0, int nc, float threshold, int* __restrict__ counts,
+                                                            const long* __restrict__ offsets, int* __restrict__ nbr, long nbr_len) {
+  using S = Shape<E64>;
+  constexpr int AR = S::AR, NB = S::NB, CB = S::CB, CT = S::CT;
+  __shared__ __attribute__((aligned(16))) float cl[CT * S::EP];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
   const long row0 = (long)blockIdx.x * AR + w * (NB * 16);
-  f32x4 rows[NB][KB];
+  f32x4 rows[NB][S::KB];
   int run[NB], self[NB];                                                    // hits so far (state included); the row's own library index, -1 past the end
   long at[NB];                                                              // where the row's list starts in nbr
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const long rr = row0 + b * 16 + c;
-    const long row = min(rr, (long)n - 1);                                  // rows past the end: a valid address, never counted or written
-    const float* fp = f + row * ldf + g * 4;
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) rows[b][kb] = *reinterpret_cast<const f32x4*>(fp + kb * 16);
+    const long row = load_row_block<E64>(f, ldf, rr, n, g, rows[b]);        // (rows past the end are never counted or written)
     run[b] = counts[row];
     self[b] = rr < n ? r0 + (int)rr : -1;
     at[b] = EMIT ? offsets[row] : 0;
   }
-  f32x4 pre[LD4];
-  auto fetch = [&](int t) {
-#pragma unroll
-    for (int i = 0; i < LD4; ++i) {
-      const int e = tid + i * NT, r = e / (E / 4), e4 = e % (E / 4);
-      const int j = min(t * CT + r, nc - 1);                                // columns past the chunk: a valid address, dropped below
-      pre[i] = *reinterpret_cast<const f32x4*>(col + (long)j * ldc + e4 * 4);
-    }
-  };
-  auto stage = [&]() {
-#pragma unroll
-    for (int i = 0; i < LD4; ++i) {
-      const int e = tid + i * NT, r = e / (E / 4), e4 = e % (E / 4);
-      *reinterpret_cast<f32x4*>(cl + r * EP + e4 * 4) = pre[i];
-    }
-  };
-  const int tiles = (nc + CT - 1) / CT;
-  fetch(0);
-  stage();
-  __syncthreads();
-  for (int t = 0; t < tiles; ++t) {
-    if (t + 1 < tiles) fetch(t + 1);
+  RowScan<E64> scan(col, ldc, nc, cl);
+  for (int t = 0; t < scan.tiles; ++t) {
     f32x4 acc[CB][NB];
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-      for (int b = 0; b < NB; ++b) acc[cb][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* ap = cl + c * EP + g * 4;
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      f32x4 a[CB];
-#pragma unroll
-      for (int cb = 0; cb < CB; ++cb) a[cb] = *reinterpret_cast<const f32x4*>(ap + cb * 16 * EP + kb * 16);
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-          for (int b = 0; b < NB; ++b) acc[cb][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cb][m], rows[b][kb][m], acc[cb][b], 0, 0, 0);
-    }
-    // D: column (lane & 15) = row of the block, row 4 g + r = column of the block.  Bit (b * CB + cb) * 4 + r of `mine`: that pair is a hit.
+    scan.scores(t, rows, acc);
+    // Bit (b * CB + cb) * 4 + r of `mine`: that pair is a hit.
     uint32_t mine = 0;
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb)
@@ -137,11 +93,7 @@ __global__ __launch_bounds__(NT) void sim_range(const float* __restrict__ f, lon
           run[b] += all;
         }
     }
-    __syncthreads();
-    if (t + 1 < tiles) {
-      stage();
-      __syncthreads();
-    }
+    scan.next(t);
   }
 #pragma unroll
   for (int b = 0; b < NB; ++b)
@@ -204,33 +156,18 @@ __global__ __launch_bounds__(NT) void leader_finish(const int* __restrict__ coun
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t l = __shfl_xor((uint32_t)best, o, 64), h = __shfl_xor((uint32_t)(best >> 32), o, 64);
-    const uint64_t other = ((uint64_t)h << 32) | l;
+    const uint64_t other = shfl_xor64(best, o);
     best = other > best ? other : best;
   }
   if (lane == 0) leader[i] = best == 0 ? -1 : (int)(0xffffffffu - (uint32_t)best);
 }
 
-template <int E64>
-void launch_range(const float* f, long ldf, long r0, long n, const float* c, long ldc, long c0, long nc, float threshold, int* counts,
-                  const long* offsets, int* nbr, long nbr_len, hipStream_t stream) {
-  const dim3 grid((unsigned)((n + AR - 1) / AR));
-  if (nbr != nullptr)
-    hipLaunchKernelGGL((sim_range<E64, true>), grid, dim3(NT), 0, stream, f, ldf, (int)r0, (int)n, c, ldc, (int)c0, (int)nc, threshold, counts,
-                       offsets, nbr, nbr_len);
-  else
-    hipLaunchKernelGGL((sim_range<E64, false>), grid, dim3(NT), 0, stream, f, ldf, (int)r0, (int)n, c, ldc, (int)c0, (int)nc, threshold, counts,
-                       offsets, nbr, nbr_len);
-}
-
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int spmm_sim_range(const float* f, long ldf, long r0, long n, const float* c, long ldc, long c0, long nc, int E, float threshold,
                               int* counts, const long* offsets, int* nbr, long nbr_len, spmm_stream_t stream) {
-  SPMM_CHECK_SHAPE(E >= 64 && E <= 512 && E % 64 == 0, "spmm_sim_range: E=%d must be a multiple of 64 up to 512", E);
-  SPMM_CHECK_SHAPE(n >= 0 && n <= 0x7fffff00L, "spmm_sim_range: n=%ld must be in [0, 2^31 - 256] rows", n);
+  if (int e = check_width("spmm_sim_range", E)) return e;
+  if (int e = check_rows("spmm_sim_range", n)) return e;
   SPMM_CHECK_SHAPE(nc >= 0 && nc <= 0x7fffff00L, "spmm_sim_range: nc=%ld must be in [0, 2^31 - 256] columns per chunk", nc);
   SPMM_CHECK_SHAPE(r0 >= 0 && r0 + n <= 0x7fffffffL, "spmm_sim_range: r0=%ld with n=%ld must keep row indices in [0, 2^31 - 1)", r0, n);
   SPMM_CHECK_SHAPE(c0 >= 0 && c0 + nc <= 0x7fffffffL, "spmm_sim_range: c0=%ld with nc=%ld must keep column indices in [0, 2^31 - 1)", c0, nc);
@@ -242,20 +179,17 @@ extern "C" int spmm_sim_range(const float* f, long ldf, long r0, long n, const f
   if (n == 0 || nc == 0) return SPMM_OK;
   SPMM_CHECK_SHAPE(counts, "spmm_sim_range: null counts (the state)");
   SPMM_CHECK_SHAPE(aligned(counts, 4), "spmm_sim_range: misaligned counts (4 bytes)");
-  SPMM_CHECK_SHAPE(f && c, "spmm_sim_range: null f / c");
-  SPMM_CHECK_SHAPE(aligned(f, 16) && aligned(c, 16), "spmm_sim_range: f / c must be 16-byte aligned");
-  SPMM_CHECK_SHAPE(ldf >= E && ldf % 4 == 0 && ldc >= E && ldc % 4 == 0, "spmm_sim_range: ldf=%ld ldc=%ld must be multiples of 4, at least E=%d",
-                   ldf, ldc, E);
-  switch (E / 64) {
-    case 1: launch_range<1>(f, ldf, r0, n, c, ldc, c0, nc, threshold, counts, offsets, nbr, nbr_len, stream); break;
-    case 2: launch_range<2>(f, ldf, r0, n, c, ldc, c0, nc, threshold, counts, offsets, nbr, nbr_len, stream); break;
-    case 3: launch_range<3>(f, ldf, r0, n, c, ldc, c0, nc, threshold, counts, offsets, nbr, nbr_len, stream); break;
-    case 4: launch_range<4>(f, ldf, r0, n, c, ldc, c0, nc, threshold, counts, offsets, nbr, nbr_len, stream); break;
-    case 5: launch_range<5>(f, ldf, r0, n, c, ldc, c0, nc, threshold, counts, offsets, nbr, nbr_len, stream); break;
-    case 6: launch_range<6>(f, ldf, r0, n, c, ldc, c0, nc, threshold, counts, offsets, nbr, nbr_len, stream); break;
-    case 7: launch_range<7>(f, ldf, r0, n, c, ldc, c0, nc, threshold, counts, offsets, nbr, nbr_len, stream); break;
-    default: launch_range<8>(f, ldf, r0, n, c, ldc, c0, nc, threshold, counts, offsets, nbr, nbr_len, stream); break;
-  }
+  if (int e = check_operands("spmm_sim_range", f, ldf, c, ldc, E)) return e;
+  dispatch_width(E, [&](auto e64) {
+    constexpr int E64 = decltype(e64)::value, AR = Shape<E64>::AR;
+    const dim3 grid((unsigned)((n + AR - 1) / AR)), block(Shape<E64>::NT);
+    if (nbr != nullptr)
+      hipLaunchKernelGGL((sim_range<E64, true>), grid, block, 0, stream, f, ldf, (int)r0, (int)n, c, ldc, (int)c0, (int)nc, threshold, counts,
+                         offsets, nbr, nbr_len);
+    else
+      hipLaunchKernelGGL((sim_range<E64, false>), grid, block, 0, stream, f, ldf, (int)r0, (int)n, c, ldc, (int)c0, (int)nc, threshold, counts,
+                         offsets, nbr, nbr_len);
+  });
   SPMM_LAUNCH_CHECK("spmm_sim_range");
   return SPMM_OK;
 }

@@ -2,23 +2,20 @@
 // (spmm_sim_topk, include/spmm_hip.h).
 //
 // Two launches.  sim_topk_part: workgroup (s, qt) walks the 256-row tiles s, s + S, .. of the chunk for the 16 queries of tile qt.  A tile's
-// 16 x 256 similarities come from the exact f32-input MFMA (v_mfma_f32_16x16x4_f32: a k-ordered fmaf chain per output element) into LDS;
-// each wave then owns four of the queries and keeps their k best candidates in registers, one per lane, sorted (best in lane 0): a score
-// is compared with the list's k-th entry first, and the few that pass are inserted by one ballot and one lane shift.  The lists go to the
-// workspace as [S, Q, k] keys.  sim_topk_merge: one workgroup per query folds the S partial lists (and, merge = 1, the state already
-// there) into the state.
+// 16 x 256 similarities come from the exact f32-input MFMA into LDS; each wave then owns four of the queries and keeps their k best
+// candidates in registers, one per lane, sorted (best in lane 0): a score is compared with the list's k-th entry first, and the few that
+// pass are inserted by one ballot and one lane shift.  The lists go to the workspace as [S, Q, k] keys.  sim_topk_merge: one workgroup per
+// query folds the S partial lists (and, merge = 1, the state already there) into the state.
 //
-// Order.  A candidate is the pair (score, library index); candidates are totally ordered -- larger score first, equal scores by ascending
-// index, NaN below every number, an empty slot below everything -- so "the k best of a set" does not depend on how the set was cut into
-// tiles, workgroups or chunks.  The score of (query, row) is one accumulator's chain over k in one fixed order (below), whatever tile,
-// lane or chunk the row falls in.  Hence any chunking of a library gives the same bits.  No floating-point atomics anywhere.
-//
-// Order of the sum over E: lane (c, g) of a wave (c = lane & 15, g = lane >> 4) loads 16 bytes -- elements 16 kb + 4 g .. + 3 of its row --
-// and feeds component m to the m-th of four MFMAs, whose k slot is g: the chain runs kb ascending, then m, then g.
-#include "common.h"
+// The order of candidates and the order of the sum over E are csrc/sim_scan.h's: "the k best of a set" does not depend on how the set was
+// cut into tiles, workgroups or chunks, and a pair's score is the same chain whatever tile, lane or chunk the row falls in.  Hence any
+// chunking of a library gives the same bits.  No floating-point atomics anywhere.
+#include "sim_scan.h"
 #include "../../include/spmm_hip.h"
 
 namespace {
+
+using namespace sim_scan;
 
 constexpr int QT = 16;            // queries of a workgroup (the MFMA's 16 output rows)
 constexpr int TR = 256;           // library rows of a tile: 4 waves x 4 blocks of 16
@@ -26,27 +23,7 @@ constexpr int TRP = TR + 4;       // score tile row stride in LDS (the four lane
 constexpr int NT = 256;
 constexpr long IDX_EMPTY = 0x7fffffffffffffffL;
 
-// Monotonic image of a score: larger float <-> larger key; -0 = +0; NaN -> 0, below -inf's image (0x007fffff).
-__device__ __forceinline__ uint32_t score_key(float s) {
-  if (s != s) return 0u;
-  if (s == 0.0f) s = 0.0f;
-  const uint32_t u = __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_score(uint32_t k) {
-  if (k == 0u) return __uint_as_float(0x7fc00000u);
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
-  const uint32_t lo = __shfl((uint32_t)v, src, 64), hi = __shfl((uint32_t)(v >> 32), src, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t shfl_up64(uint64_t v) {
-  const uint32_t lo = __shfl_up((uint32_t)v, 1, 64), hi = __shfl_up((uint32_t)(v >> 32), 1, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-// ---- first launch: candidates of a chunk as 64-bit keys (score image << 32 | ~row): a larger key is a better candidate, 0 is empty
+// ---- first launch: candidates of a chunk as 64-bit keys (sim_scan.h's pack_key over the row within the chunk)
 __device__ __forceinline__ void list_insert(uint64_t& mine, uint64_t cand, int lane) {
   const int pos = __popcll(__ballot(mine > cand));
   const uint64_t up = shfl_up64(mine);
@@ -119,7 +96,7 @@ __global__ __launch_bounds__(NT) void sim_topk_part(const float* __restrict__ q,
       for (int j = 0; j < 4; ++j) {
         const int row = tile0 + lane + 64 * j;
         const uint32_t sk = score_key(sl[ql_i * TRP + lane + 64 * j]);
-        const uint64_t key = ((uint64_t)sk << 32) | (0xffffffffu - (uint32_t)row);
+        const uint64_t key = pack_key(sk, (uint32_t)row);
         bool ok = row < n && key > thr[u];
         if (has_cut) ok = ok && ic[u] >= 0 && (sk < kc[u] || (sk == kc[u] && base + row > ic[u]));
         uint64_t mask = __ballot(ok);
@@ -199,8 +176,8 @@ __global__ __launch_bounds__(NT) void sim_topk_merge(const uint64_t* __restrict_
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const bool real = v[j] != 0;
-      list2_offer(L, real ? (uint32_t)(v[j] >> 32) : 0u, real ? base + (long)(0xffffffffu - (uint32_t)v[j]) : IDX_EMPTY, k, lane);
+      const bool real = v[j] != EMPTY_KEY;
+      list2_offer(L, real ? key_image(v[j]) : 0u, real ? base + (long)key_index(v[j]) : IDX_EMPTY, k, lane);
     }
   }
   lk[w][lane] = L.key;
@@ -237,27 +214,25 @@ extern "C" int spmm_sim_topk(const float* q, long ldq, const float* f, long ldf,
                              long* index, int merge, const float* cut_scores, const long* cut_index, void* workspace, long workspace_bytes,
                              spmm_stream_t stream) {
   SPMM_CHECK_SHAPE(k >= 1 && k <= 64, "spmm_sim_topk: k=%d must be in [1,64]", k);
-  SPMM_CHECK_SHAPE(E >= 64 && E <= 512 && E % 64 == 0, "spmm_sim_topk: E=%d must be a multiple of 64 up to 512", E);
+  if (int e = check_width("spmm_sim_topk", E)) return e;
   SPMM_CHECK_SHAPE(Q >= 1, "spmm_sim_topk: Q=%d must be at least 1", Q);
   SPMM_CHECK_SHAPE(Q <= 65535 * QT, "spmm_sim_topk: Q=%d exceeds %d queries per call", Q, 65535 * QT);
   SPMM_CHECK_SHAPE(n >= 0 && n <= 0x7fffff00L, "spmm_sim_topk: n=%ld must be in [0, 2^31 - 256] rows per chunk", n);   // (row numbers of the last, partial tile stay in int)
   SPMM_CHECK_SHAPE(merge == 0 || merge == 1, "spmm_sim_topk: merge=%d must be 0 or 1", merge);
   SPMM_CHECK_SHAPE(scores && index, "spmm_sim_topk: null scores / index (the state)");
-  SPMM_CHECK_SHAPE((reinterpret_cast<uintptr_t>(scores) & 3) == 0 && (reinterpret_cast<uintptr_t>(index) & 7) == 0,
-                   "spmm_sim_topk: misaligned scores / index (4 / 8 bytes)");
+  SPMM_CHECK_SHAPE(aligned(scores, 4) && aligned(index, 8), "spmm_sim_topk: misaligned scores / index (4 / 8 bytes)");
   SPMM_CHECK_SHAPE((cut_scores == nullptr) == (cut_index == nullptr), "spmm_sim_topk: cut_scores and cut_index come together");
   SPMM_CHECK_SHAPE(base >= 0 && base <= IDX_EMPTY - 0x80000000L, "spmm_sim_topk: base=%ld out of range", base);
   if (n == 0 && merge == 1) return SPMM_OK;                                 // nothing seen: the state stays as it is
   int S = 0;
   if (n > 0) {
     SPMM_CHECK_SHAPE(q && f, "spmm_sim_topk: null q / f");
-    SPMM_CHECK_SHAPE((reinterpret_cast<uintptr_t>(q) & 15) == 0 && (reinterpret_cast<uintptr_t>(f) & 15) == 0,
-                     "spmm_sim_topk: q / f must be 16-byte aligned");
+    SPMM_CHECK_SHAPE(aligned(q, 16) && aligned(f, 16), "spmm_sim_topk: q / f must be 16-byte aligned");
     SPMM_CHECK_SHAPE(ldq >= E && ldq % 4 == 0 && ldf >= E && ldf % 4 == 0,
                      "spmm_sim_topk: ldq=%ld ldf=%ld must be multiples of 4, at least E=%d", ldq, ldf, E);
     S = splits_of(Q, n);
     const long need = (long)S * Q * k * 8;
-    SPMM_CHECK_SHAPE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && workspace_bytes >= need,
+    SPMM_CHECK_SHAPE(workspace && aligned(workspace, 16) && workspace_bytes >= need,
                      "spmm_sim_topk: workspace of %ld bytes (16-byte aligned) needed, %ld given (spmm_sim_topk_workspace_bytes)", need,
                      workspace ? workspace_bytes : 0L);
     const size_t lds = (size_t)(QT * (E + 4) + QT * TRP) * sizeof(float);     // at most 49 664 bytes (E = 512)

@@ -23,6 +23,16 @@ def _tiny_train_model(env, dropout=True):
     return m.train()
 
 
+def _strided(x, extra, lead):
+    """x [r, E] on the device inside a wider NaN-filled matrix: row stride E + extra, first element `lead` floats in (16-byte aligned)."""
+    import torch
+    r, E = x.shape
+    w = torch.full((max(r, 1), E + extra), float("nan"), device="cuda")
+    v = w[:r, lead:lead + E]
+    v.copy_(torch.as_tensor(x))
+    return v
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Host model of csrc/common.h's counter-based generator: the ONE model of it in the tests.
 # ---------------------------------------------------------------------------------------------------------------------

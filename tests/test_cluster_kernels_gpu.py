@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import kmeans_reference as R
+from helpers_gpu import _strided
 
 pytestmark = pytest.mark.gpu
 
@@ -23,15 +24,6 @@ KS = [1, 15, 16, 17, 64, 65, 300]
 ASSIGN_CASES = [(64, n, K) for i, n in enumerate(NS) for j, K in enumerate(KS) if (i + j) % 2 == 0] + \
                [(256, n, K) for i, n in enumerate(NS) for j, K in enumerate(KS) if (i + j) % 4 == 1]
 PAD = 16
-
-
-def _strided(x, extra, lead):
-    """x [r, E] on the device inside a wider NaN-filled matrix: row stride E + extra, first element `lead` floats in (16-byte aligned)."""
-    r, E = x.shape
-    w = torch.full((max(r, 1), E + extra), float("nan"), device="cuda")
-    v = w[:r, lead:lead + E]
-    v.copy_(torch.as_tensor(x))
-    return v
 
 
 def _state(n, best0=7.0, idx0=12345):

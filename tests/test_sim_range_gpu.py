@@ -12,20 +12,12 @@ import pytest
 import torch
 
 import butina_reference as B
+from helpers_gpu import _strided
 
 pytestmark = pytest.mark.gpu
 
 PAD = 16
 C_PAD, N_PAD = 12345, -777
-
-
-def _strided(x, extra, lead):
-    """x [r, E] on the device inside a wider NaN-filled matrix: row stride E + extra, first element `lead` floats in (16-byte aligned)."""
-    r, E = x.shape
-    w = torch.full((max(r, 1), E + extra), float("nan"), device="cuda")
-    v = w[:r, lead:lead + E]
-    v.copy_(torch.as_tensor(x))
-    return v
 
 
 def _sweep(f, c, t, r0, c0, col_cuts, row_cuts, offsets, nbr_len):
