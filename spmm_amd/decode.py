@@ -1,7 +1,12 @@
 """PV -> SMILES k-beam decoding (BASELINE.json configs[3]): N molecules x k beams per launch with
 a key/value cache, returning per molecule the hypotheses the reference's one-molecule, whole-prefix-per-step search
 (`generate`, d_pv2smiles_single.py:26-51; `evaluate`, d_pv2smiles_batched.py:18-59) returns.  That sequential search is
-restated in oracle/decode_oracle.py -- test infrastructure, the yard-stick of tests/ -- not here."""
+restated in oracle/decode_oracle.py -- test infrastructure, the yard-stick of tests/ -- not here.
+How the searches are put together: `make_decoder` builds the decoder of every search (K/V cache or whole-prefix forwards, with or without
+a warp, one half or two); a decoder's `step` / `prefill` return logits that have gone their last mile (`_Decoder.finish`: grammar mask
+on the raw logits, then the warp), so a search masks exactly once and never asks what class it drives; `_start` begins the beam
+searches (`_search`, behind beam_search_batched, generate_with_property and predict_products) and the distinct one (sample_distinct)
+alike; `_advance` is the one position of the former, `_GumbelNoise` the seeded noise of both."""
 from __future__ import annotations
 
 import functools
@@ -18,14 +23,14 @@ CLS_ID, SEP_ID = 2, 3           # vocab_bpe_300.txt:3-4
 GRAPH_BELOW_ROWS = 200          # measured break-even of graph=True, not a switch (replay is opt-in): with the bookkeeping in one launch a position is a
 #                                 chain of ~130 dependent kernels (1.95 ms at 100 rows, 2.2 at 1 000, 3.6 at 5 000) and replay gains 7 % at 100 rows, 2 % at
 #                                 250, nothing from 500 on -- and a replayed graph has a fixed batch: no compaction of finished molecules
-last_run: dict = {}             # what the last eager beam_search_batched did: molecules, compactions, final_batch, positions, prefix_tokens, prefill,
-#                                 guidance, temperature, top_k, top_p, baseline_rows (0, or the N*k rows of the all-masked branch), syntax (bool),
-#                                 dropped_masked (finals a constrained search dropped: they went through a masked token)
+last_run: dict = {}             # what the last eager _search did: molecules, compactions, final_batch, positions, prefix_tokens, prefill, the decoder's
+#                                 warp_info (guidance, temperature, top_k, top_p, baseline_rows: 0, or the N*k rows of the all-masked half), syntax
+#                                 (the decoder carried a mask), dropped_masked (finals a constrained search dropped: they went through a masked token)
 COMPACT_BELOW = 0.75            # the batch is re-gathered once at most this share of its molecules is still live
 FUSED_BEAM_STEP = True          # beam bookkeeping of a position as one HIP launch (spmm_beam_step); False: the tensor-op form (BeamBook.update)
 GUMBEL_SALT = 0x50563253        # call-site salt of the sampled search's noise ("PV2S"; dropout and negative sampling use small integers)
-last_generate: dict = {}        # what the last generate_with_property did: samples, no_final, chunks, prefix_tokens, guidance, temperature, top_k, top_p,
-#                                 baseline_rows (of the last chunk), syntax (bool), dropped_masked (summed over the chunks)
+last_generate: dict = {}        # what the last generate_with_property did: samples, no_final, chunks, prefix_tokens, the warp_info of the last chunk's
+#                                 decoder (last_run's five), syntax (bool), dropped_masked (summed over the chunks)
 
 
 def _pick(p: torch.Tensor, k: int, stochastic: bool, generator=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -80,22 +85,28 @@ def gumbel_noise_host(seed: int, salt: int, mol_ids, t: int, k: int, V: int, Lma
 
 
 class _GumbelNoise:
-    """The noise of one seeded search: `noise(t, mol)` -> fp32 [n * k, V] after `t` generated tokens, for the molecules now in the batch
-    (mol: BeamBook.mol, None = all N).  On the device into one buffer where spmm_gumbel_noise takes the shape (k <= 8, V <= 512,
-    Lmax <= 256: whatever the one-launch beam step takes), else the host form -- which only ever serves the whole batch."""
+    """The noise of one seeded search, beam or distinct: `noise(t, mol)` -> [n * k, V] for the position t of the last token held, for the
+    molecules now in the batch (mol: BeamBook.mol, None = all).  ids (host int64 [N]): the GLOBAL molecule every molecule of the batch
+    draws as -- mol_base + n for the beam searches, (pv_base + g) * 128 + slot // 8 for the distinct one.  On the device (fp32, one
+    buffer) where spmm_gumbel_noise takes the shape (k <= 8, V <= 512, Lmax <= 256: whatever the one-launch steps take), else the host
+    form in float64 -- which only ever serves the whole batch."""
 
-    def __init__(self, seed: int, mol_base: int, N: int, k: int, V: int, Lmax: int, device, on_device: bool):
-        self.seed, self.mol_base, self.N, self.shape, self.device = seed, mol_base, N, (k, V, Lmax), device
-        self.buf = torch.empty(N * k, V, dtype=torch.float32, device=device) if on_device else None
+    def __init__(self, seed: int, salt: int, ids: torch.Tensor, k: int, V: int, Lmax: int, device, on_device: bool):
+        self.seed, self.salt, self.ids, self.shape, self.device = seed, salt, ids, (k, V, Lmax), device
+        self.buf = torch.empty(ids.numel() * k, V, dtype=torch.float32, device=device) if on_device else None
         if on_device:
             self.seed_dev = torch.tensor([(int(seed) & _M64) - ((int(seed) & (1 << 63)) << 1)], dtype=torch.int64, device=device)
+            self.ids_dev = ids.to(torch.int32).to(device)
+            self.mol = self.live = None                  # the last compaction seen and the ids of its molecules
 
     def __call__(self, t: int, mol: torch.Tensor | None = None) -> torch.Tensor:
         k, V, Lmax = self.shape
         if self.buf is None:
-            return gumbel_noise_host(self.seed, GUMBEL_SALT, range(self.mol_base, self.mol_base + self.N), t, k, V, Lmax).to(torch.float32).to(self.device)
-        n = self.N if mol is None else mol.numel()
-        return ops.gumbel_noise(self.seed_dev, n, k, V, Lmax, salt=GUMBEL_SALT, t=t, mol=mol, mol_base=self.mol_base, out=self.buf[:n * k])
+            return gumbel_noise_host(self.seed, self.salt, self.ids.tolist(), t, k, V, Lmax).to(self.device)
+        if mol is not None and mol is not self.mol:      # (gathered once per compaction, not per position)
+            self.mol, self.live = mol, self.ids_dev[mol.long()]
+        ids = self.ids_dev if mol is None else self.live
+        return ops.gumbel_noise(self.seed_dev, ids.numel(), k, V, Lmax, salt=self.salt, t=t, mol=ids, out=self.buf[:ids.numel() * k])
 
 
 def _pick_seeded(logits: torch.Tensor, noise: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -363,7 +374,6 @@ class BeamBook:
         per beam, finals, survivors, token histories, `anc` -- all in place.  Returns the tokens to feed next (int32 [N*k]).  With t_ptr
         (device int32 [1]) the number of tokens held comes from device memory (*t_ptr + t_off) and self.t is left to the caller.  With noise
         (fp32 [N*k, V]) the k successors of a beam are the k largest of logits + noise: the sampled search."""
-        from . import ops
         ids = ops.beam_step(logits, self, t=self.t, t_ptr=t_ptr, t_off=t_off, anc=anc, ids_out=ids_out, rowmap=rowmap, noise=noise)
         if t_ptr is None:
             self.t += 1
@@ -404,7 +414,47 @@ def _prefix_rows(prefix_ids: torch.Tensor, pair_of_molecule, N: int, k: int) -> 
     return pom, (first * k).to(torch.int32)
 
 
-class RecomputeDecoder:
+def _decoder_warp(k: int, min_keep: int | None, base_embeds, memory=None, **controls) -> dict:
+    """The warp a decoder carries, checked: check_warp's four controls (all at their defaults: NO_WARP) and min_keep (None: k), the tokens
+    every row keeps whatever the truncation says -- k for the searches that draw k tokens per row, 1 for sample_distinct, whose rows
+    contribute any number of candidates."""
+    if memory is not None:
+        raise ValueError("guidance contrasts a property condition with the all-masked one; a decoder with memory= (reaction prediction) "
+                         "has no such baseline")
+    min_keep = k if min_keep is None else int(min_keep)
+    warp = check_warp(k=min_keep, **controls) or dict(NO_WARP)
+    if base_embeds is None and warp["guidance"] != 1.0:
+        raise ValueError(f"guidance={warp['guidance']} needs base_embeds, the encoded all-masked PV")
+    return dict(warp, min_keep=min_keep)
+
+
+class _Decoder:
+    """What the searches ask of every decoder beyond the forward pass: the last mile of its logits.  `step` and `prefill` return what
+    `finish` makes of the raw next-token logits -- a constrained search's grammar mask (`premask`, a SyntaxMask) first, on the RAW logits,
+    then the warp the decoder carries (`carry_warp`) -- and with neither, the raw logits themselves: no launch, no tensor op."""
+    cached = False                                       # one token per step against a K/V cache (CachedDecoder and its kin)
+    premask = None
+    warp, fused_warp = None, False                       # _decoder_warp's dict; the warp is ops.logit_warp (else warp_logits)
+    warp_info = dict(NO_WARP, baseline_rows=0)           # what last_run records: the four controls, and the rows of the all-masked half
+    xkv_once = None                                      # (cached: the cross-attention projections a later decoder on the same conditions takes)
+
+    def carry_warp(self, warp: dict, baseline_rows: int = 0, fused: bool = False):
+        self.warp, self.fused_warp = warp, fused
+        self.warp_info = dict({f: warp[f] for f in NO_WARP}, baseline_rows=baseline_rows)
+
+    def finish(self, lc: torch.Tensor, lu: torch.Tensor | None = None, by: str = "row") -> torch.Tensor:
+        """Raw logits lc [n, V] -- and lu, those of the rows' all-masked twins -- -> what the search reads.  by: SyntaxMask's."""
+        if self.premask is not None:                     # both halves alike: masking lc alone would be wrong for guidance <= 0
+            self.premask(lc, lu, by=by)
+        w = self.warp
+        if w is None:
+            return lc
+        if self.fused_warp:
+            return ops.logit_warp(lc, lu, w=w["guidance"], temperature=w["temperature"], top_k=w["top_k"], top_p=w["top_p"], min_keep=w["min_keep"])
+        return warp_logits(lc.float(), None if lu is None else lu.float(), **w)
+
+
+class RecomputeDecoder(_Decoder):
     """Step function with the reference's cost model: re-runs the whole prefix of every beam through the module API
     (`model.text_encoder(..., is_decoder=True, return_logits=True)`), so it works with the CPU oracle as well."""
 
@@ -414,12 +464,15 @@ class RecomputeDecoder:
         self.device = prop_embeds.device
         self.tok = torch.zeros(self.kv.shape[0], Lmax, dtype=torch.long, device=self.device)
 
-    def step(self, ids: torch.Tensor, t: int) -> torch.Tensor:
+    def _forward(self, ids: torch.Tensor, t: int) -> torch.Tensor:
         self.tok[:, t] = ids
         text = self.tok[:, : t + 1]
         return self.m.text_encoder(text, attention_mask=torch.ones_like(text), encoder_hidden_states=self.kv,
                                    encoder_attention_mask=torch.ones(self.kv.shape[:-1], dtype=torch.long, device=self.device),
                                    return_dict=True, is_decoder=True, return_logits=True)[:, -1, :]
+
+    def step(self, ids: torch.Tensor, t: int) -> torch.Tensor:
+        return self.finish(self._forward(ids, t))
 
     def prefill(self, prefix_ids: torch.Tensor, pair_of_molecule, by_steps: bool = False) -> torch.Tensor:
         """CachedDecoder.prefill for the whole-prefix forward: the rows are seeded with their prefix tokens -> logits [Npairs, V] for
@@ -428,7 +481,7 @@ class RecomputeDecoder:
         rows = prefix_ids.to(self.device).long()[pom.to(self.device)].repeat_interleave(self.k, dim=0)        # [N*k, P]
         P = rows.shape[1]
         self.tok[:, :P - 1] = rows[:, :P - 1]
-        return self.step(rows[:, P - 1], P - 1)[dst.to(self.device).long()]
+        return self.finish(self._forward(rows[:, P - 1], P - 1)[dst.to(self.device).long()], by="pair")
 
     def reorder(self, parent: torch.Tensor, t: int):
         N, k = parent.shape
@@ -446,11 +499,13 @@ def _cross_kv(eng, bert_pfx: str, c, rows: torch.Tensor) -> dict:
     return out
 
 
-class CachedDecoder:
+class CachedDecoder(_Decoder):
     """One new token per beam per step on the HIP engine: per-layer self-attention K/V cache [R, Lmax, H] that is never
     moved (the ancestry table `anc[r, j]` names the cache row holding position j of row r's hypothesis), cross-attention
     K/V projected once per molecule and shared by its k beams (cache slots sketched at
-    xbert.py:291-295,480,1344-1348)."""
+    xbert.py:291-295,480,1344-1348).  Carrying a warp (`carry_warp`: temperature, top-k, nucleus -- no guidance, which needs the second
+    half of GuidedDecoder) it warps with the kernel where the one-launch beam step runs (k <= 8, V <= 512, FUSED_BEAM_STEP)."""
+    cached = True
 
     def __init__(self, model, prop_embeds: torch.Tensor | None, k: int, Lmax: int, repeat: int = 1, xkv: dict | None = None, memory: dict | None = None,
                  src: torch.Tensor | None = None):
@@ -478,7 +533,8 @@ class CachedDecoder:
             assert memory is None and repeat == 1 and int(self.src.min()) >= 0 and int(self.src.max()) < N
             N = self.src.numel()
         N *= repeat
-        assert Lmax <= 256 and H == c.hidden_size and c.hidden_size // c.num_attention_heads == 64
+        check_positions(Lmax)
+        assert H == c.hidden_size and c.hidden_size // c.num_attention_heads == 64
         self.N, self.R, self.Lmax, self.Lp, self.H = N, N * k, Lmax, Lkv, H
         # head-major cache [R, nH, Lmax, 64]: the positions of a (row, head) are one contiguous 128-B-per-key stream for the wave that reads them
         self.kc = [torch.empty(self.R, c.num_attention_heads, Lmax, 64, dtype=BF, device=dev) for _ in range(c.num_hidden_layers)]
@@ -505,6 +561,9 @@ class CachedDecoder:
         else:
             self.xkv = {l: (KV.view(-1, Lkv, 2 * H).repeat_interleave(self.repeat, dim=0).reshape(-1, 2 * H) if self.repeat > 1 else KV)
                         for l, KV in xkv.items()}
+
+    def carry_warp(self, warp: dict, baseline_rows: int = 0):
+        super().carry_warp(warp, baseline_rows, fused=bool(FUSED_BEAM_STEP and self.k <= 8 and self.c.vocab_size <= 512))
 
     def search_tables(self) -> Tuple[torch.Tensor, torch.Tensor | None]:
         """(anc, rowmap) as the search's beam step updates / reads them: the rows of the beams it keeps books for."""
@@ -543,9 +602,14 @@ class CachedDecoder:
 
     @torch.no_grad()
     def step(self, ids: torch.Tensor, t: int, t_dev: torch.Tensor | None = None) -> torch.Tensor:
-        """ids [R]: the token at position t of every beam -> fp32 logits [R, V] for position t + 1.
+        """ids [R]: the token at position t of every beam -> fp32 logits [R, V] for position t + 1 (`finish` of the raw ones).
         t_dev (int32 [1], device): the position comes from device memory instead (t is then ignored), which makes the whole
         launch sequence independent of the step -- capturable once as a hipGraph and replayed (beam_search_batched(graph=True))."""
+        return self.finish(self._forward(ids, t, t_dev))
+
+    @torch.no_grad()
+    def _forward(self, ids: torch.Tensor, t: int, t_dev: torch.Tensor | None = None) -> torch.Tensor:
+        """`step` up to the raw logits, on all R rows the decoder holds."""
         P, c, R, H, nH, new = self.P, self.c, self.R, self.H, self.c.num_attention_heads, self.eng._new
         bp = self.pfx + "bert."
         # residual sublayers: the engine's (inference: no tape, dropout off -- the row kernel then never reads the seed)
@@ -589,8 +653,14 @@ class CachedDecoder:
         row of the first molecule that starts from the pair, and `anc[:, :P]` of every row names that row: the cache is never copied per
         beam, and positions that all beams of a molecule read from one row are the attention kernel's shared-key fast path.  The LM head
         runs on the pairs' last-position rows only.
-        by_steps=True: the twin on existing kernels only -- the prefix fed through `step` position by position on all N*k rows, identity
-        ancestry: the parity yard-stick and the timing baseline, not meant to be fast."""
+        by_steps=True: the twin on existing kernels only -- the prefix fed through the raw step position by position on all N*k rows,
+        identity ancestry: the parity yard-stick and the timing baseline, not meant to be fast.
+        Either way the raw logits of position P are finished once, by pair: a grammar mask reads the prefixes and nothing before them."""
+        return self.finish(self._prefill(prefix_ids, pair_of_molecule, by_steps), by="pair")
+
+    @torch.no_grad()
+    def _prefill(self, prefix_ids: torch.Tensor, pair_of_molecule, by_steps: bool) -> torch.Tensor:
+        """`prefill` up to the raw logits [Npairs, V]."""
         from .engine import BF, KVSource, Group, Batch
         if self.mem is not None:
             raise ValueError("prefill: prompted decoding is for the PV decoder; a decoder with memory= (reaction prediction) has none")
@@ -603,7 +673,7 @@ class CachedDecoder:
         if by_steps:
             rows = ids_h[pom].repeat_interleave(k, dim=0).to(dev)               # [N*k, P]
             for j in range(P):
-                logits = self.step(rows[:, j].contiguous(), j)
+                logits = self._forward(rows[:, j].contiguous(), j)
             return logits[dst.to(dev).long()]
         eng.train_mode = False
         TP, f, n = self.pfx + "bert.", c.fusion_layer, c.num_hidden_layers
@@ -644,8 +714,8 @@ class CachedDecoder:
 
 
 class GuidedDecoder(CachedDecoder):
-    """CachedDecoder whose `step` / `prefill` return WARPED logits (warp_logits' rules): temperature, top-k and nucleus truncation, and --
-    with base_embeds -- classifier-free guidance against the decoder's own all-masked prediction.
+    """CachedDecoder with classifier-free guidance against the decoder's own all-masked prediction (base_embeds) in its warp, next to
+    temperature, top-k and nucleus truncation (warp_logits' rules).
     Guidance runs both conditions in ONE set of launches: the decoder holds 2N molecules, rows [0, R) on their conditions and rows
     [R, 2R) on the baseline (R = N * k), the all-masked PV encoded and projected once (base_embeds [1, Lp, H]: with every property
     masked the encoding does not depend on the PV) and its keys | values shared by all N baseline molecules: their cross-attention is a
@@ -655,56 +725,36 @@ class GuidedDecoder(CachedDecoder):
     The baseline half's ancestry is the mirror anc[R + r, j] = anc[r, j] + R0 (R0: the uncompacted R; cache rows keep their indices
     under compaction, so the offset is constant), refreshed by one small launch at the head of every step.
     The scores the search records are log-probabilities of the warped distribution, renormalised over the kept tokens.
-    The warp is the kernel where the one-launch beam step runs (k <= 8, V <= 512, FUSED_BEAM_STEP), else warp_logits."""
+    A warp without guidance needs no second half: it is CachedDecoder's own (`carry_warp`; make_decoder)."""
 
     def __init__(self, model, prop_embeds: torch.Tensor, k: int, Lmax: int, repeat: int = 1, xkv: dict | None = None, memory: dict | None = None, *,
                  base_embeds: torch.Tensor | None = None, guidance: float = 1.0, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                  min_keep: int | None = None):
-        """min_keep (None: k): the tokens every row keeps whatever the truncation says -- k for the searches that draw k tokens per row, 1
-        for sample_distinct, whose rows contribute any number of candidates."""
-        if memory is not None:
-            raise ValueError("guidance contrasts a property condition with the all-masked one; a decoder with memory= (reaction prediction) "
-                             "has no such baseline")
-        self.min_keep = k if min_keep is None else int(min_keep)
-        self.warp = check_warp(guidance, temperature, top_k, top_p, self.min_keep) or dict(NO_WARP)
-        if base_embeds is None and self.warp["guidance"] != 1.0:
-            raise ValueError(f"guidance={guidance} needs base_embeds, the encoded all-masked PV")
+        """min_keep: _decoder_warp's."""
+        warp = _decoder_warp(k, min_keep, base_embeds, memory, guidance=guidance, temperature=temperature, top_k=top_k, top_p=top_p)
+        if base_embeds is None:
+            raise ValueError("a guided decoder needs base_embeds, the encoded all-masked PV, for its second half")
         Nc = prop_embeds.shape[0]
-        self.guided = base_embeds is not None
-        if self.guided:
-            N = Nc * repeat
-            conds = torch.cat([prop_embeds, base_embeds[:1].to(prop_embeds.device).to(prop_embeds.dtype)], dim=0)
-            src = torch.cat([torch.arange(Nc).repeat_interleave(repeat), torch.full((N,), Nc, dtype=torch.int64)])
-            super().__init__(model, conds, k, Lmax, xkv=xkv, src=src)
-        else:
-            super().__init__(model, prop_embeds, k, Lmax, repeat=repeat, xkv=xkv)
-        self.R0 = self.R // 2 if self.guided else self.R                  # beam rows of the search before any compaction
-        self.fused_warp = bool(FUSED_BEAM_STEP and k <= 8 and self.c.vocab_size <= 512)
-        self.warp_info = dict(self.warp, baseline_rows=self.R0 if self.guided else 0)
-        self.premask = None                                               # a constrained search's SyntaxMask: on the raw logits, before the warp
+        conds = torch.cat([prop_embeds, base_embeds[:1].to(prop_embeds.device).to(prop_embeds.dtype)], dim=0)
+        src = torch.cat([torch.arange(Nc).repeat_interleave(repeat), torch.full((Nc * repeat,), Nc, dtype=torch.int64)])
+        super().__init__(model, conds, k, Lmax, xkv=xkv, src=src)
+        self.R0 = self.R // 2                                             # beam rows of the search before any compaction
+        self.carry_warp(warp, baseline_rows=self.R0)
 
-    def _warped(self, logits: torch.Tensor, n: int, by: str = "row") -> torch.Tensor:
-        """logits fp32 [2n, V] (guided: conditioned rows, then their baseline twins) or [n, V] -> warped [n, V], in place where the kernel runs."""
-        w = self.warp
-        lc, lu = logits[:n], (logits[n:] if self.guided else None)
-        if self.premask is not None:                                      # both halves alike: masking lc alone would be wrong for w <= 0
-            self.premask(lc, lu, by=by)
-        if self.fused_warp:
-            return ops.logit_warp(lc, lu, w=w["guidance"], temperature=w["temperature"], top_k=w["top_k"], top_p=w["top_p"], min_keep=self.min_keep)
-        return warp_logits(lc, lu, guidance=w["guidance"], temperature=w["temperature"], top_k=w["top_k"], top_p=w["top_p"], min_keep=self.min_keep)
+    def finish(self, logits: torch.Tensor, lu=None, by: str = "row") -> torch.Tensor:
+        """Raw fp32 [2n, V], the conditioned rows and then their baseline twins (lu is not passed: it is the second half) -> warped [n, V],
+        in place where the kernel runs."""
+        n = logits.shape[0] // 2
+        return super().finish(logits[:n], logits[n:], by)
 
     def _expand_xkv(self, xkv: dict):
         """The conditioned half as CachedDecoder expands it; the baseline half reads ONE copy, the all-masked row's projection."""
-        if not self.guided:
-            return super()._expand_xkv(xkv)
         Lp, H, n = self.Lp, self.H, self.N // 2
         pick = self.src[:n].to(self.device)
         self.xkv = {l: KV.view(-1, Lp, 2 * H).index_select(0, pick).reshape(-1, 2 * H) for l, KV in xkv.items()}
         self.xkv_base = {l: KV.view(-1, Lp, 2 * H)[-1] for l, KV in xkv.items()}        # [Lp, 2H] views of xkv_once
 
     def _compact_xkv(self, keep: torch.Tensor):
-        if not self.guided:
-            return super()._compact_xkv(keep)
         n = self.N // 2                                                   # (keep = the kept slots of the first half, then their twins)
         for l, KV in self.xkv.items():
             self.xkv[l] = KV.view(n, self.Lp, KV.shape[1])[keep[:keep.numel() // 2]].reshape(-1, KV.shape[1]).contiguous()
@@ -712,98 +762,75 @@ class GuidedDecoder(CachedDecoder):
     def _cross_attn(self, l: int, q: torch.Tensor, ctx: torch.Tensor):
         """Two launches: the conditioned rows on their molecules' keys | values, the baseline rows all on the one all-masked block
         (sequence stride 0: every molecule's "own" block is block 0)."""
-        if not self.guided:
-            return super()._cross_attn(l, q, ctx)
         H, nH, R, KV, B = self.H, self.c.num_attention_heads, self.R // 2, self.xkv[l], self.xkv_base[l]
         ops.decode_attn(q[:R], KV[:, :H], KV[:, H:], ctx[:R], nH=nH, Lkv=self.Lp, seq_stride=self.Lp * 2 * H, tok_stride=2 * H, kv_div=self.k, group=self.k)
         ops.decode_attn(q[R:], B[:, :H], B[:, H:], ctx[R:], nH=nH, Lkv=self.Lp, seq_stride=0, tok_stride=2 * H, kv_div=self.k, group=self.k)
 
     def search_tables(self):
-        R = self.R // 2 if self.guided else self.R
+        R = self.R // 2
         return self.anc[:R], (None if self.rowmap is None else self.rowmap[:R])
 
     @torch.no_grad()
     def step(self, ids: torch.Tensor, t: int, t_dev: torch.Tensor | None = None) -> torch.Tensor:
         """ids [R]: the token at position t of every beam of the search -> warped fp32 logits [R, V] for position t + 1."""
-        if not self.guided:
-            return self._warped(super().step(ids, t, t_dev), self.R)
         R = self.R // 2
         assert ids.numel() == R, (ids.shape, R)
         torch.add(self.anc[:R], self.R0, out=self.anc[R:])               # the mirror: what the beam step did to the first half since the last step
         ids = ids.to(torch.int32)
-        return self._warped(super().step(torch.cat([ids, ids]), t, t_dev), R)
+        return self.finish(self._forward(torch.cat([ids, ids]), t, t_dev))
 
     @torch.no_grad()
     def compact(self, keep: torch.Tensor):
         """`keep` (slots of the search's batch) -> the same molecules of both halves."""
-        super().compact(torch.cat([keep, keep + self.N // 2]) if self.guided else keep)
+        super().compact(torch.cat([keep, keep + self.N // 2]))
 
     @torch.no_grad()
     def reorder(self, parent: torch.Tensor, t):
-        super().reorder(torch.cat([parent, parent], dim=0) if self.guided else parent, t)
+        super().reorder(torch.cat([parent, parent], dim=0), t)
 
     @torch.no_grad()
-    def prefill(self, prefix_ids: torch.Tensor, pair_of_molecule, by_steps: bool = False) -> torch.Tensor:
-        """CachedDecoder.prefill -> the WARPED logits [Npairs, V] of the pairs.  Guided: every (condition, prefix) pair gets a baseline twin
-        (pair p + Npairs, the start of the baseline molecules of p's molecules), so the unimodal layers still run once per distinct
-        prefix, and the twin's cache row is the pair's + R0 -- what the mirror expects."""
-        k, N = self.k, (self.N // 2 if self.guided else self.N)
-        pom, dst = _prefix_rows(prefix_ids, pair_of_molecule, N, k)
-        n_pairs = prefix_ids.shape[0]
-        if by_steps:                                                      # the stepping twin: this class's own (two-half, warped) step
-            rows = prefix_ids.detach().cpu().to(torch.int64)[pom].repeat_interleave(k, dim=0).to(self.device)
-            premask = self.premask                                        # (the mask belongs to the last position's logits alone)
-            try:
-                for j in range(rows.shape[1]):
-                    self.premask = premask if j == rows.shape[1] - 1 else None
-                    logits = self.step(rows[:, j].contiguous(), j)
-            finally:
-                self.premask = premask
-            return logits[dst.to(self.device).long()]
-        if not self.guided:
-            return self._warped(super().prefill(prefix_ids, pom), n_pairs, by="pair")
-        logits = super().prefill(torch.cat([prefix_ids, prefix_ids], dim=0), torch.cat([pom, pom + n_pairs]))
-        return self._warped(logits, n_pairs, by="pair")
+    def _prefill(self, prefix_ids: torch.Tensor, pair_of_molecule, by_steps: bool) -> torch.Tensor:
+        """Every (condition, prefix) pair gets a baseline twin (pair p + Npairs, the start of the baseline molecules of p's molecules): the
+        unimodal layers still run once per distinct prefix, the twin's cache row is the pair's + R0 -- what the mirror expects (by_steps:
+        a fresh decoder's identity ancestry is its own mirror) -- and the raw logits come back as `finish` reads them, pairs then twins."""
+        pom, _ = _prefix_rows(prefix_ids, pair_of_molecule, self.N // 2, self.k)
+        return super()._prefill(torch.cat([prefix_ids, prefix_ids], dim=0), torch.cat([pom, pom + prefix_ids.shape[0]]), by_steps)
 
 
-class GuidedRecompute:
-    """GuidedDecoder's twin on whole-prefix forwards (RecomputeDecoder: any model with the module API, the CPU oracle included): one
-    decoder per condition and warp_logits.  The yard-stick of the cached route."""
+class GuidedRecompute(_Decoder):
+    """The warping decoders' twin on whole-prefix forwards (RecomputeDecoder: any model with the module API, the CPU oracle included): one
+    decoder per condition -- they return raw logits, carrying neither mask nor warp -- and warp_logits.  The yard-stick of the cached route."""
 
     def __init__(self, model, prop_embeds: torch.Tensor, k: int, Lmax: int, *, base_embeds: torch.Tensor | None = None, guidance: float = 1.0,
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, min_keep: int | None = None):
-        self.min_keep = k if min_keep is None else int(min_keep)         # (GuidedDecoder's)
-        self.warp = check_warp(guidance, temperature, top_k, top_p, self.min_keep) or dict(NO_WARP)
-        if base_embeds is None and self.warp["guidance"] != 1.0:
-            raise ValueError(f"guidance={guidance} needs base_embeds, the encoded all-masked PV")
+        warp = _decoder_warp(k, min_keep, base_embeds, guidance=guidance, temperature=temperature, top_k=top_k, top_p=top_p)
         self.k, self.device = k, prop_embeds.device
-        self.cond = RecomputeDecoder(model, prop_embeds, k, Lmax)
-        self.base = None if base_embeds is None else RecomputeDecoder(model, base_embeds[:1].expand(prop_embeds.shape[0], -1, -1), k, Lmax)
-        self.warp_info = dict(self.warp, baseline_rows=0 if self.base is None else prop_embeds.shape[0] * k)
-        self.premask = None                                               # as GuidedDecoder's
-
-    def _warped(self, lc, lu, by: str = "row"):
-        w = self.warp
-        if self.premask is not None:
-            self.premask(lc, lu, by=by)
-        return warp_logits(lc.float(), None if lu is None else lu.float(), guidance=w["guidance"], temperature=w["temperature"], top_k=w["top_k"],
-                           top_p=w["top_p"], min_keep=self.min_keep)
+        self.halves = [RecomputeDecoder(model, prop_embeds, k, Lmax)]
+        if base_embeds is not None:
+            self.halves.append(RecomputeDecoder(model, base_embeds[:1].expand(prop_embeds.shape[0], -1, -1), k, Lmax))
+        self.carry_warp(warp, baseline_rows=(len(self.halves) - 1) * prop_embeds.shape[0] * k)
 
     def step(self, ids: torch.Tensor, t: int) -> torch.Tensor:
-        return self._warped(self.cond.step(ids, t), None if self.base is None else self.base.step(ids, t))
+        return self.finish(*[d.step(ids, t) for d in self.halves])
 
     def prefill(self, prefix_ids: torch.Tensor, pair_of_molecule, by_steps: bool = False) -> torch.Tensor:
-        return self._warped(self.cond.prefill(prefix_ids, pair_of_molecule), None if self.base is None else self.base.prefill(prefix_ids, pair_of_molecule),
-                            by="pair")
+        return self.finish(*[d.prefill(prefix_ids, pair_of_molecule) for d in self.halves], by="pair")
 
     def reorder(self, parent: torch.Tensor, t: int):
-        self.cond.reorder(parent, t)
-        if self.base is not None:
-            self.base.reorder(parent, t)
+        for d in self.halves:
+            d.reorder(parent, t)
 
 
 PAD_ID = 0
 DECODE_MAXL = 256              # positions the decode kernels hold (spmm_decode_attn, spmm_beam_step, spmm_gumbel_noise)
+
+
+def check_positions(Lmax: int, P: int | None = None) -> int:
+    """The positions a search holds, Lmax = P + max_steps + 2 (P given: spelled out in the message) -> Lmax, or ValueError beyond DECODE_MAXL."""
+    if Lmax > DECODE_MAXL:
+        how = "" if P is None else f"P + max_steps + 2 = {P} + {Lmax - P - 2} + 2 = "
+        raise ValueError(f"{how}{Lmax} positions exceed the {DECODE_MAXL} the decode kernels hold (max_steps counts positions after the prefix)")
+    return Lmax
 
 
 def check_prefix(prefix, N: int, vocab_size: int | None, max_steps: int) -> torch.Tensor | None:
@@ -834,11 +861,8 @@ def check_prefix(prefix, N: int, vocab_size: int | None, max_steps: int) -> torc
         raise ValueError(f"prefix: [SEP] ({SEP_ID}) or PAD ({PAD_ID}) inside a prefix")
     if int(p.min()) < 0 or (vocab_size is not None and int(p.max()) >= vocab_size):
         raise ValueError(f"prefix: token id {int(p.max()) if int(p.min()) >= 0 else int(p.min())} outside the vocabulary of {vocab_size}")
-    P = p.shape[1]
-    if P + max_steps + 2 > DECODE_MAXL:
-        raise ValueError(f"prefix: P + max_steps + 2 = {P} + {max_steps} + 2 = {P + max_steps + 2} positions exceed the {DECODE_MAXL} the decode "
-                         "kernels hold (max_steps counts positions after the prefix)")
-    return None if P == 1 else p
+    check_positions(p.shape[1] + max_steps + 2, p.shape[1])
+    return None if p.shape[1] == 1 else p
 
 
 def _vocab_size(model) -> int | None:
@@ -899,23 +923,19 @@ def beam_search_batched(model, props: torch.Tensor, k: int = 5, max_steps: int =
     if cached is None:
         cached = hasattr(model, "engine")
     prefix = check_prefix(prefix, props.shape[0], _vocab_size(model), max_steps)
-    syntax = syntax_table(model, syntax, prefix, max_steps)
+    table = syntax_table(model, syntax, prefix, max_steps)
     prop_embeds = encode_properties(model, props, prop_mask)
     if cached:
         model.engine.train_mode = False
     N = prop_embeds.shape[0]
     P = 1 if prefix is None else prefix.shape[1]
-    if warp is None:
-        dec = (CachedDecoder if cached else RecomputeDecoder)(model, prop_embeds, k, P + max_steps + 2)
-    else:
-        base = _baseline_embeds(model, props[:1]) if warp["guidance"] != 1.0 else None
-        dec = (GuidedDecoder if cached else GuidedRecompute)(model, prop_embeds, k, P + max_steps + 2, base_embeds=base, **warp)
-        graph = False
+    base = _baseline_embeds(model, props[:1]) if warp is not None and warp["guidance"] != 1.0 else None      # (guidance = 1 never builds it)
+    dec = make_decoder(model, prop_embeds, k, P + max_steps + 2, cached, warp, base_embeds=base)
     if prefix is not None:
         prefix = prefix.expand(N, P)                     # one (PV, prefix) pair per molecule; equal prefixes share the unimodal layers
     return _search(model, dec, N, k=k, max_steps=max_steps, sync_every=sync_every, stochastic=stochastic, generator=generator,
                    graph=bool(graph), compact=compact, seed=seed, mol_base=mol_base, prefix=prefix, pair_of_molecule=range(N), prefill=prefill,
-                   syntax=syntax)
+                   table=table)
 
 
 def _baseline_embeds(model, pv: torch.Tensor) -> torch.Tensor:
@@ -924,17 +944,32 @@ def _baseline_embeds(model, pv: torch.Tensor) -> torch.Tensor:
     return encode_properties(model, pv, torch.ones(1, pv.shape[1], device=pv.device))
 
 
+def make_decoder(model, prop_embeds: torch.Tensor, k: int, Lmax: int, cached: bool, warp: dict | None, *, base_embeds: torch.Tensor | None = None,
+                 repeat: int = 1, xkv: dict | None = None, min_keep: int | None = None):
+    """The decoder of a search over `repeat` molecules per row of prop_embeds, k rows each: on the K/V cache (cached) or on whole-prefix
+    forwards, carrying `warp` (check_warp's result; None: none) with min_keep (_decoder_warp's), in two halves when base_embeds (the
+    encoded all-masked PV) asks for guidance.  xkv: `xkv_once` of an earlier decoder of this call on the same conditions (None from a
+    whole-prefix one, which projects nothing).  The searches know a decoder by `step`, `prefill`, `reorder` / `search_tables`,
+    `compact`, `premask`, `warp`, `warp_info`, `cached` and `xkv_once`, never by its class."""
+    if not cached:
+        pe = prop_embeds if repeat == 1 else prop_embeds.repeat_interleave(repeat, dim=0)
+        return RecomputeDecoder(model, pe, k, Lmax) if warp is None else GuidedRecompute(model, pe, k, Lmax, base_embeds=base_embeds, min_keep=min_keep, **warp)
+    if warp is not None and base_embeds is not None:
+        return GuidedDecoder(model, prop_embeds, k, Lmax, repeat=repeat, xkv=xkv, base_embeds=base_embeds, min_keep=min_keep, **warp)
+    dec = CachedDecoder(model, prop_embeds, k, Lmax, repeat=repeat, xkv=xkv)
+    if warp is not None:
+        dec.carry_warp(_decoder_warp(k, min_keep, None, **warp))
+    return dec
+
+
 def _advance(dec, book: BeamBook, ids: torch.Tensor, t: int, *, t_dev: torch.Tensor | None = None, noise=None, pick=None,
-             ids_out: torch.Tensor | None = None, premask=None) -> torch.Tensor:
+             ids_out: torch.Tensor | None = None) -> torch.Tensor:
     """One position of the search: the tokens `ids` at position t of every beam row -> the tokens at position t + 1, with the book and the
     decoder's ancestry brought up to date -- by the one-launch beam step (book.fused) or by pick, BeamBook.update and reorder.
     t_dev (int32 [1], device; cached decoder): the position comes from device memory in every launch and t is ignored, so the call can
     be captured once and replayed.  noise: the seeded search's source (_GumbelNoise).  pick(logits [N, k, V], noise) -> (log-probs, ids)
-    [N, k, k]: the candidates of the tensor-op form (None: the k most probable).  ids_out: static buffer that receives the result.
-    premask: a constrained search's SyntaxMask for a decoder that returns raw logits (a guided one applies it itself, before its warp)."""
+    [N, k, k]: the candidates of the tensor-op form (None: the k most probable).  ids_out: static buffer that receives the result."""
     logits = dec.step(ids, t) if t_dev is None else dec.step(ids, t, t_dev=t_dev)
-    if premask is not None:
-        premask(logits)
     noise = None if noise is None else noise(t, book.mol)
     if book.fused:
         anc, rowmap = dec.search_tables()
@@ -948,50 +983,44 @@ def _advance(dec, book: BeamBook, ids: torch.Tensor, t: int, *, t_dev: torch.Ten
     return ids if ids_out is None else ids_out.copy_(ids)
 
 
+def _start(dec, table, prefix: torch.Tensor | None, pair_of_molecule, k: int, max_steps: int, *, kernel: bool, prefill: bool = True):
+    """The start of a search on a fresh decoder whose molecules have k rows each: molecule n starts from prefix[pair_of_molecule[n]]
+    (check_prefix's result, int64 [Npairs, P], P >= 2: `prefill`, or with prefill=False its stepping twin) or, prefix None, from [CLS]
+    alone.  table (syntax_table's result): the search is constrained, and its SyntaxMask (kernel: SyntaxMask's) becomes the decoder's
+    `premask` before the first logits are taken.  -> (the logits of the first free position per row [len(pair_of_molecule) * k, V] --
+    the k rows of a molecule hold the same history, so they are equal -- and the mask or None)."""
+    pom = torch.as_tensor(pair_of_molecule).to(torch.int64)
+    mask = None
+    if table is not None:
+        mask = SyntaxMask(table, k, 1 if prefix is None else int(prefix.shape[1]), max_steps, dec.device, kernel=kernel)
+        mask.start(prefix, pom, len(pom))
+    dec.premask = mask
+    if prefix is None:
+        return dec.step(torch.full((len(pom) * k,), CLS_ID, dtype=torch.long, device=dec.device), 0), mask
+    return dec.prefill(prefix, pom, by_steps=not prefill)[pom.repeat_interleave(k).to(dec.device)], mask
+
+
 def _search(model, dec, N: int, *, k: int, max_steps: int, sync_every: int = 4, stochastic: bool = False, generator=None, graph: bool = False,
             compact: bool = True, seed: int | None = None, mol_base: int = 0, need: int | None = None, prefix: torch.Tensor | None = None,
-            pair_of_molecule=None, prefill: bool = True, syntax=None):
+            pair_of_molecule=None, prefill: bool = True, table=None):
     """beam_search_batched behind the decoder's construction (generate_with_property builds its decoders from one encoded PV).
-    need: finals that end a molecule's search (BeamBook; None: k).  prefix (check_prefix's result, int64 [Npairs, P], P >= 2) with
-    pair_of_molecule [N]: molecule n starts from prefix[pair_of_molecule[n]] (CachedDecoder.prefill; prefill=False: its stepping twin);
-    the decoder was built for Lmax = P + max_steps + 2.  syntax: beam_search_batched's (the table, True, or None / False)."""
+    need: finals that end a molecule's search (BeamBook; None: k).  prefix, pair_of_molecule (None: one pair per molecule), prefill,
+    table: `_start`'s; the decoder was built for Lmax = P + max_steps + 2."""
     last_run.clear()
-    cached, dev = isinstance(dec, CachedDecoder), dec.device
+    dev = dec.device
+    pom = torch.arange(N) if pair_of_molecule is None else torch.as_tensor(pair_of_molecule).to(torch.int64)
     P = 1 if prefix is None else int(prefix.shape[1])
-    if prefix is not None and P + max_steps + 2 > DECODE_MAXL:
-        raise ValueError(f"P + max_steps + 2 = {P} + {max_steps} + 2 exceeds the {DECODE_MAXL} positions the decode kernels hold")
     Lmax = P + max_steps + 2
     seeded = bool(stochastic and seed is not None)
     # one launch per position for the beam bookkeeping (csrc/decode.hip::beam_step_kernel: k <= 8 beams, vocabulary <= 512, histories <= 256
     # tokens -- the tensor-op bookkeeping serves everything else); spmm_gumbel_noise and spmm_smiles_mask accept the same shapes
-    fits = bool(cached and k <= 8 and model.cfg.text.vocab_size <= 512 and Lmax <= 256)
+    fits = bool(dec.cached and k <= 8 and model.cfg.text.vocab_size <= 512 and Lmax <= DECODE_MAXL)
     fused = bool(fits and FUSED_BEAM_STEP and (seeded or not stochastic))
-    table = syntax_table(model, syntax, prefix, max_steps)
-    mask = None
-    if table is not None:
-        mask = SyntaxMask(table, k, P, max_steps, dev, kernel=fused)
-        mask.start(prefix, pair_of_molecule, N)
-    # the mask sits on the raw logits: a guided decoder applies it itself, in front of its warp; for the others this function does
-    if hasattr(dec, "premask"):
-        dec.premask, own_mask = mask, None
-    else:
-        own_mask = mask
-    if prefix is None:
-        ids = torch.full((N * k,), CLS_ID, dtype=torch.long, device=dev)
-        logits = dec.step(ids, 0)
-        if own_mask is not None:
-            own_mask(logits, by="row")
-        logits = logits.view(N, k, -1)[:, 0].float()                        # all k rows hold the same [CLS] prefix
-    else:
-        pom = torch.as_tensor(pair_of_molecule).to(torch.int64)
-        logits = dec.prefill(prefix, pom, by_steps=not prefill)
-        if own_mask is not None:
-            own_mask(logits, by="pair")
-        logits = logits[pom.to(dev)].float()             # [N, V]: the k rows of a molecule hold the same prefix
-        prefix = prefix[pom]
+    logits, mask = _start(dec, table, prefix, pom, k, max_steps, kernel=fused, prefill=prefill)
+    logits = logits.view(N, k, -1)[:, 0].float()         # [N, V]: beam 0's
     V = logits.shape[-1]
-    book = BeamBook(N, k, max_steps, dev, fused=fused, need=need, prefix=prefix)
-    noise_at = _GumbelNoise(seed, mol_base, N, k, V, Lmax, dev, on_device=fits) if seeded else None
+    book = BeamBook(N, k, max_steps, dev, fused=fused, need=need, prefix=None if prefix is None else prefix[pom])
+    noise_at = _GumbelNoise(seed, GUMBEL_SALT, mol_base + torch.arange(N), k, V, Lmax, dev, on_device=fits) if seeded else None
 
     def pick(logits, noise):
         if stochastic and not seeded and mask is not None:
@@ -1006,13 +1035,13 @@ def _search(model, dec, N: int, *, k: int, max_steps: int, sync_every: int = 4, 
     ids = indices.reshape(N * k)
     if mask is not None:
         mask.book = book                                 # from here on the histories are the book's
-    if graph and cached and not stochastic and prefix is None and not hasattr(dec, "warp_info") and mask is None:
+    if graph and dec.cached and not stochastic and prefix is None and dec.warp is None and dec.premask is None:
         return _decode_graphed(dec, book, ids, max_steps, sync_every)
     n_cur = N
     last_run.update(molecules=N, compactions=0, final_batch=N, positions=0, prefix_tokens=P, prefill=bool(prefix is not None and prefill),
-                    **getattr(dec, "warp_info", dict(NO_WARP, baseline_rows=0)), syntax=mask is not None, dropped_masked=0)
+                    **dec.warp_info, syntax=mask is not None, dropped_masked=0)
     for s in range(max_steps):
-        ids = _advance(dec, book, ids, P + s, noise=noise_at, pick=pick, premask=own_mask)
+        ids = _advance(dec, book, ids, P + s, noise=noise_at, pick=pick)
         last_run["positions"] = s + 1
         if s % sync_every != sync_every - 1:
             continue
@@ -1043,6 +1072,34 @@ def _search(model, dec, N: int, *, k: int, max_steps: int, sync_every: int = 4, 
     return res
 
 
+def _decode_graphed(dec, book: BeamBook, ids: torch.Tensor, max_steps: int, sync_every: int):
+    """The loop of beam_search_batched with every step-dependent scalar in device memory: two eager positions (they also set the
+    kernels' one-time attributes), then one captured position replayed for the rest."""
+    ids_s = ids.to(torch.int32).clone() if book.fused else ids.clone()      # static: the position's output is the next position's input
+    t_dev = torch.ones(1, dtype=torch.int32, device=ids.device)  # position of the token in ids_s
+
+    def one_position():
+        _advance(dec, book, ids_s, 0, t_dev=t_dev, ids_out=ids_s)
+        t_dev.add_(1)
+
+    eager = min(2, max_steps)
+    for _ in range(eager):
+        one_position()
+    steps_left = max_steps - eager
+    if steps_left > 0 and not book.all_done():
+        g = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):      # other threads' GPU work does not abort this capture
+            one_position()
+        g.replay()                                               # capture records, it does not execute: this is position `eager`
+        for s in range(1, steps_left):
+            if s % sync_every == 0 and book.all_done():
+                break
+            g.replay()
+    book.t = int(t_dev.item()) + 1
+    return book.results()
+
+
 @torch.no_grad()
 def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: torch.Tensor | None = None, k: int = 2, stochastic: bool = True,
                            seed: int = 0, max_steps: int = 100, chunk: int | None = None, prefix=None, prefill: bool = True, guidance: float = 1.0,
@@ -1067,7 +1124,7 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
     warp = check_warp(guidance, temperature, top_k, top_p, k)
     cached = hasattr(model, "engine")
     prefix = check_prefix(prefix, 1, _vocab_size(model), max_steps)
-    syntax = syntax_table(model, syntax, prefix, max_steps)
+    table = syntax_table(model, syntax, prefix, max_steps)
     P = 1 if prefix is None else prefix.shape[1]
     prop_embeds = encode_properties(model, pv.reshape(1, -1), None if prop_mask is None else prop_mask.reshape(1, -1))
     if cached:
@@ -1079,19 +1136,10 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
     base_embeds = _baseline_embeds(model, pv) if warp is not None and warp["guidance"] != 1.0 else None
     for base in range(0, n_sample, chunk):
         n = min(chunk, n_sample - base)
-        if warp is not None:
-            if cached:
-                dec = GuidedDecoder(model, prop_embeds, k, P + max_steps + 2, repeat=n, xkv=xkv, base_embeds=base_embeds, **warp)
-                xkv = dec.xkv_once
-            else:
-                dec = GuidedRecompute(model, prop_embeds.expand(n, -1, -1), k, P + max_steps + 2, base_embeds=base_embeds, **warp)
-        elif cached:
-            dec = CachedDecoder(model, prop_embeds, k, P + max_steps + 2, repeat=n, xkv=xkv)
-            xkv = dec.xkv_once
-        else:
-            dec = RecomputeDecoder(model, prop_embeds.expand(n, -1, -1), k, P + max_steps + 2)
+        dec = make_decoder(model, prop_embeds, k, P + max_steps + 2, cached, warp, base_embeds=base_embeds, repeat=n, xkv=xkv)
+        xkv = dec.xkv_once                               # projected by the first chunk's decoder, taken by the later ones
         res = _search(model, dec, n, k=k, max_steps=max_steps, stochastic=stochastic, seed=seed if stochastic else None, mol_base=base,
-                      prefix=prefix, pair_of_molecule=[0] * n, prefill=prefill, syntax=syntax)
+                      prefix=prefix, pair_of_molecule=[0] * n, prefill=prefill, table=table)
         dropped += last_run.get("dropped_masked", 0)
         for finals in res:
             if not finals:
@@ -1101,7 +1149,7 @@ def generate_with_property(model, pv: torch.Tensor, n_sample: int, prop_mask: to
                 out.append(finals[rng.randrange(len(finals)) if stochastic else 0][1])
     last_generate.clear()
     last_generate.update(samples=n_sample, no_final=none, chunks=(n_sample + chunk - 1) // chunk, prefix_tokens=P,
-                         **{f: last_run.get(f, v) for f, v in dict(NO_WARP, baseline_rows=0).items()}, syntax=syntax is not None,
+                         **{f: last_run.get(f, v) for f, v in dict(NO_WARP, baseline_rows=0).items()}, syntax=table is not None,
                          dropped_masked=dropped)
     return out
 
@@ -1244,7 +1292,7 @@ def sample_distinct(model, props: torch.Tensor, n_distinct: int, prop_mask: torc
     exceeds its parent's, and so the first n slots of a wider search ARE the n-slot search: one seed gives one ordered list of distinct
     sequences, and asking for more extends it.
     One launch per position for the bookkeeping where spmm_sbs_step takes the shape (cached decoder, vocabulary <= 512, <= 256 positions,
-    FUSED_BEAM_STEP), the float64 tensor-op form elsewhere.  The decoder is CachedDecoder(k = 8, repeat = W / 8) reading the book's current
+    FUSED_BEAM_STEP), the float64 tensor-op form elsewhere.  The decoder is the cached one (make_decoder: k = 8, repeat = W / 8) reading the book's current
     ancestry table (cached=False: the whole-prefix decoder); a finished slot's row keeps being stepped with token 0.  The search stays eager.
     prefix, prefill, syntax, temperature, top_k, top_p: beam_search_batched's, with min_keep = 1 (a row contributes any number of
     candidates); the log-probabilities returned are those of the warped distribution renormalised over the kept and allowed tokens.  A
@@ -1262,54 +1310,25 @@ def sample_distinct(model, props: torch.Tensor, n_distinct: int, prop_mask: torc
     prefix = check_prefix(prefix, G, _vocab_size(model), max_steps)
     table = syntax_table(model, syntax, prefix, max_steps)
     P = 1 if prefix is None else prefix.shape[1]
-    Lmax = P + max_steps + 2
-    if Lmax > DECODE_MAXL:
-        raise ValueError(f"P + max_steps + 2 = {P} + {max_steps} + 2 exceeds the {DECODE_MAXL} positions the decode kernels hold")
+    Lmax = check_positions(P + max_steps + 2, P)
     W = (n_distinct + 7) // 8 * 8
-    R = W // 8
+    k = 8 if cached else W                               # rows per decoder molecule: W / 8 molecules of 8 slots per group, or one of W
     prop_embeds = encode_properties(model, props, prop_mask)
     dev = prop_embeds.device
     if cached:
         model.engine.train_mode = False
-        dec = (CachedDecoder(model, prop_embeds, 8, Lmax, repeat=R) if warp is None else
-               GuidedDecoder(model, prop_embeds, 8, Lmax, repeat=R, min_keep=1, **warp))
-    else:
-        dec = (RecomputeDecoder(model, prop_embeds, W, Lmax) if warp is None else GuidedRecompute(model, prop_embeds, W, Lmax, min_keep=1, **warp))
+    dec = make_decoder(model, prop_embeds, k, Lmax, cached, warp, repeat=W // k, min_keep=1)
     V = _vocab_size(model)
     fused = bool(cached and FUSED_BEAM_STEP and V is not None and 4 <= V <= 512)
-    mask = None
-    pom = torch.arange(G * R) // R if cached else torch.arange(G)        # the (PV, prefix) pair of every decoder molecule: its group
     if prefix is not None:
         prefix = prefix.expand(G, P)
-    if table is not None:
-        mask = SyntaxMask(table, 8 if cached else W, P, max_steps, dev, kernel=fused)
-        mask.start(prefix, pom, len(pom))
-    if hasattr(dec, "premask"):
-        dec.premask, own_mask = mask, None
-    else:
-        own_mask = mask
-    if prefix is None:
-        logits = dec.step(torch.full((G * W,), CLS_ID, dtype=torch.long, device=dev), 0)
-        if own_mask is not None:
-            own_mask(logits, by="row")
-    else:
-        logits = dec.prefill(prefix, pom, by_steps=not prefill)              # [G, V]: one pair per group
-        if own_mask is not None:
-            own_mask(logits, by="pair")
-        logits = logits.repeat_interleave(W, dim=0)
+    # the (PV, prefix) pair of every decoder molecule is its group
+    logits, mask = _start(dec, table, prefix, torch.arange(G * W // k) // (W // k), k, max_steps, kernel=fused, prefill=prefill)      # [G*W, V]
     V = logits.shape[-1]
     book = DistinctBook(G, W, max_steps, dev, fused=fused, prefix=prefix, anc=dec.anc if cached else None)
-    mols = ((pv_base + torch.arange(G))[:, None] * 128 + torch.arange(R)[None, :]).reshape(-1)
-    if fused:
-        seed_dev = torch.tensor([(int(seed) & _M64) - ((int(seed) & (1 << 63)) << 1)], dtype=torch.int64, device=dev)
-        mol_dev = mols.to(torch.int32).to(dev)
-        nbuf = torch.empty(G * W, V, dtype=torch.float32, device=dev)
-
-    def noise(t):
-        """Keyed by the absolute position of the last token held, as the seeded beam search keys its draws."""
-        if fused:
-            return ops.gumbel_noise(seed_dev, G * R, 8, V, Lmax, salt=DISTINCT_SALT, t=t, mol=mol_dev, out=nbuf)
-        return gumbel_noise_host(seed, DISTINCT_SALT, mols.tolist(), t, 8, V, Lmax)
+    # keyed by the absolute position of the last token held, as the seeded beam search keys its draws
+    noise = _GumbelNoise(seed, DISTINCT_SALT, ((pv_base + torch.arange(G))[:, None] * 128 + torch.arange(W // 8)[None, :]).reshape(-1), 8, V, Lmax, dev,
+                         on_device=fused)
 
     def advance(logits):
         ids = book.step_fused(logits.float(), noise(book.t - 1)) if fused else book.update(logits, noise(book.t - 1))
@@ -1327,10 +1346,7 @@ def sample_distinct(model, props: torch.Tensor, n_distinct: int, prop_mask: torc
     for s in range(max_steps):
         if s % sync_every == 0 and int(book.open.sum().item()) == 0:         # the one host read of the loop
             break
-        logits = dec.step(ids, P + s)
-        if own_mask is not None:
-            own_mask(logits)
-        ids = advance(logits)
+        ids = advance(dec.step(ids, P + s))
         positions = s + 1
     res, unfinished, empty = book.results(n_distinct)
     kept = [[h for h in hyps if h[0] > SYNTAX_DROP_BELOW] for hyps in res]
@@ -1592,31 +1608,3 @@ def greedy_products(model, text_ids: torch.Tensor, text_mask: torch.Tensor, max_
         row = row[:max_steps + 1]
         out.append(row[:row.index(SEP_ID) + 1] if SEP_ID in row else row)
     return out
-
-
-def _decode_graphed(dec: CachedDecoder, book: BeamBook, ids: torch.Tensor, max_steps: int, sync_every: int):
-    """The loop of beam_search_batched with every step-dependent scalar in device memory: two eager positions (they also set the
-    kernels' one-time attributes), then one captured position replayed for the rest."""
-    ids_s = ids.to(torch.int32).clone() if book.fused else ids.clone()      # static: the position's output is the next position's input
-    t_dev = torch.ones(1, dtype=torch.int32, device=ids.device)  # position of the token in ids_s
-
-    def one_position():
-        _advance(dec, book, ids_s, 0, t_dev=t_dev, ids_out=ids_s)
-        t_dev.add_(1)
-
-    eager = min(2, max_steps)
-    for _ in range(eager):
-        one_position()
-    steps_left = max_steps - eager
-    if steps_left > 0 and not book.all_done():
-        g = torch.cuda.CUDAGraph()
-        torch.cuda.synchronize()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):      # other threads' GPU work does not abort this capture
-            one_position()
-        g.replay()                                               # capture records, it does not execute: this is position `eager`
-        for s in range(1, steps_left):
-            if s % sync_every == 0 and book.all_done():
-                break
-            g.replay()
-    book.t = int(t_dev.item()) + 1
-    return book.results()

@@ -71,7 +71,7 @@ def test_both_halves_follow_their_own_condition(peaky):
         assert dec.xkv_base[l].data_ptr() == once[N * Lp:].data_ptr()
     full_c, full_u = decode.RecomputeDecoder(m, pe, k, T + 6), decode.RecomputeDecoder(m, pe_u, k, T + 6)
     raw = {}
-    inner = decode.CachedDecoder.step
+    inner = decode.CachedDecoder._forward                                  # the step up to the raw logits of all 2R rows
 
     def spy(self, ids, t, t_dev=None):
         raw["logits"] = inner(self, ids, t, t_dev).clone()
@@ -79,7 +79,7 @@ def test_both_halves_follow_their_own_condition(peaky):
 
     worst = 0.0
     with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(decode.CachedDecoder, "step", spy)
+        mp.setattr(decode.CachedDecoder, "_forward", spy)
         R, live = N * k, list(range(N))
         for t in range(T):
             if t == 3:                                                       # drop the middle molecule from all three decoders
